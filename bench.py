@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the MI355X megakernel path tracer on BASELINE.json's configs.
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]     (N > 1: launched by torch.distributed.run)
 
 A "step" is one full pass of the hot path over one frame: every pixel of the workload's
 resolution x its spp through the megakernel (film accumulate included), scene already resident
@@ -10,7 +10,11 @@ the real asset is an external download, so the seeded procedural stand-in of SUR
 used).  For N > 1 the same frame is sharded by screen tile over the ranks (strong scaling) and
 the float4 film is sum-reduced to rank 0 over RCCL inside the timed region.
 
-Rank 0 prints ONE JSON line with the driver's contract plus
+Rank 0 prints ONE JSON line with the driver's contract (metric, value, unit, ms_per_step = the mean time of one of the K timed
+steps, ...).  A plain run does nothing else: set-up, W warm-up steps, the K timed steps, the line.  --dump-outputs DIR also writes
+the film of the last timed step (what a caller of the timed path receives: the float4 film, H x W x 4; rank 0's after the reduce) as
+DIR/film.npy, cut to a fixed, seeded sample of its pixels where it exceeds 64 MiB.
+--full adds everything that takes runs of its own:
   "roofline":     against the 8 TB/s HBM3E peak.  `traffic` = HBM bytes per launch from the PMC counters (FETCH_SIZE x 2 +
                   WRITE_SIZE, MI355X_MICROARCH.md), collected LIVE by this run: rocprofv3 --pmc passes of this same script on
                   the same workload AT THE TIMED SPP (round 5; round 4 measured 64 spp and scaled);
@@ -91,6 +95,22 @@ METRIC = "Msamples/s (+ fraction of HBM roofline) at fixed SPP, 1/2/4/8 GPU"
 
 
 SCENE_FILES = {}  # (workload, sampler, spp) -> the generated scene description (the PMC child processes load it instead of generating it again)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all arrays together
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: every array as <directory>/<name>.npy in float32.  An array above its share of DUMP_LIMIT_BYTES keeps a fixed,
+    seeded sample of its rows (pixels, in their order): the same rows in every run with the same arguments, so two builds compare."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = np.random.default_rng(0).choice(len(rows), share // rows[0].nbytes, replace=False)
+            a = rows[np.sort(keep)]
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def build_scene(workload: str, tmpdir: str, spp_override: int | None, sampler: str = "Independent", scene_file: str | None = None):
@@ -432,8 +452,9 @@ def roofline_block(workload, variant, kernel_ms, launch_samples, bytes_per_sampl
     return r
 
 
-def run_workload(workload, args, rank, world, local_rank, tmp, steps, warmup, spp_override=None, sampler="Independent", warmup_spp=None):
-    """times `steps` frames of one workload -> (value Msamples/s, ms_per_step, kernel_ms, variant, scene, res, spp, desc)"""
+def run_workload(workload, args, rank, world, local_rank, tmp, steps, warmup, spp_override=None, sampler="Independent", warmup_spp=None, keep_film=False):
+    """times `steps` frames of one workload -> (value Msamples/s, ms_per_step, kernel_ms, variant, scene, res, spp, desc);
+    keep_film: rank 0 keeps the last timed step's film on the host in run_workload.film"""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -504,6 +525,7 @@ def run_workload(workload, args, rank, world, local_rank, tmp, steps, warmup, sp
     kernel_ms = [step() for _ in range(steps)]
     barrier()
     elapsed = time.perf_counter() - t0
+    run_workload.film = film.cpu().numpy() if keep_film and rank == 0 else None
     mean_kernel_ms = sum(kernel_ms) / max(len(kernel_ms), 1)
     run_workload.multi_gpu = None
     if world > 1 or force:
@@ -511,6 +533,7 @@ def run_workload(workload, args, rank, world, local_rank, tmp, steps, warmup, sp
         t = torch.tensor([elapsed, mean_kernel_ms, -mean_kernel_ms, mean_reduce_ms], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, mean_kernel_ms = float(t[0]), float(t[1])
+    if (world > 1 or force) and args.full:
         # what every rank actually saw -- its device, and the size / rank of ITS communicator as RCCL reports them (lrhip_comm_info) -- gathered to
         # rank 0: the line itself says whether the collective spanned the N ranks the launcher started
         mine = reducer.info() if reducer is not None else None
@@ -560,6 +583,10 @@ def main():
                     help="sampler of the timed frame (anything but Independent invalidates the headline number)")
     ap.add_argument("--scheduler", default="auto", choices=["auto", "legacy", "pool"],
                     help="force one kernel family (lrhip_set_scheduler) for A/B and profiling runs; anything but auto is recorded in config.scheduler_override")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU legs + parity, path statistics, the other BASELINE configs, the "
+                         "reference's own code, the live PMC passes + roofline blocks, the multi-GPU film check (trimmed by the --no-* options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's film to DIR/film.npy (float32)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the cpu_baseline leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes (roofline.traffic from profiles/ or null)")
@@ -588,7 +615,8 @@ def main():
 
     with tempfile.TemporaryDirectory(prefix="lr_bench_") as tmp:
         value, ms_per_step, mean_kernel_ms, variant, scene, res, spp, desc = run_workload(
-            args.workload, args, rank, world, local_rank, tmp, args.steps, args.warmup, args.spp, args.sampler)
+            args.workload, args, rank, world, local_rank, tmp, args.steps, args.warmup, args.spp, args.sampler, keep_film=args.dump_outputs is not None)
+        film = run_workload.film
         elapsed = ms_per_step * args.steps * 1e-3
         main_multi, main_collective = getattr(run_workload, "multi_gpu", None), getattr(run_workload, "collective", None)
 
@@ -598,7 +626,7 @@ def main():
         # its own multi_gpu record (reduce_ms, what RCCL saw, the reduced film against a 1-GPU render of the same tiles).  Every rank takes part.
         multi_extra = []
         forced = os.environ.get("LR_BENCH_FORCE_COLLECTIVE") == "1" and dist.is_initialized()
-        if (world > 1 or forced) and not args.no_extra:
+        if (world > 1 or forced) and args.full and not args.no_extra:
             for w, spp_cfg in (("c4", None), ("c5", BENCH_SPP_CAP["c5"])):
                 v, ms, kms, var, sc, r, sp, d = run_workload(w, args, rank, world, local_rank, tmp, 1, 1, args.extra_spp or spp_cfg, "Independent",
                                                              warmup_spp=None if w == "c5" else min(8, args.extra_spp or 8))  # (C5: wavefront mode sizes its queues by the frame's spp)
@@ -627,102 +655,105 @@ def main():
                 out["config"]["note"] = "spp / sampler overridden: not the headline configuration"
             elif args.workload in BENCH_SPP_CAP:
                 out["config"]["note"] = f"timed at {spp} spp of the same frame (Independent sampler: throughput is spp-invariant)"
-            bytes_per_sample = ALGORITHMIC_BYTES_PER_SAMPLE[args.workload]
-            if world == 1 and not args.no_cpu_baseline:  # the CPU leg runs on rank 0 at N = 1 only
-                cpu, bytes_per_sample, _, (cpu_frame, cpu_spp) = cpu_baseline(scene, res, args.cpu_seconds)
-                out["cpu_baseline"] = cpu
-                out["parity"] = device_parity(scene, local_rank, cpu_frame, cpu_spp, args.scheduler)
-            if world == 1 and not args.no_stats:
-                stats = path_statistics(scene, local_rank, spp, args.scheduler)
-                out["rays_per_s"] = value * 1e6 * stats["rays_per_sample"]
-                out["mean_path_length"] = stats["mean_path_length"]
-                out["path_statistics"] = stats
             if main_multi:
                 out["multi_gpu"] = main_multi
                 if main_multi.get("reduced_film_equals_1gpu_render") is False:
                     out["value"] = None  # a frame that is not the frame has no throughput
                     out["error"] = "the film the collective delivered differs from a 1-GPU render of the same tiles"
-            # one launch renders this rank's shard: samples_per_step / world samples
-            launch_samples = samples_per_step / world
-            import torch
-            simds = torch.cuda.get_device_properties(local_rank).multi_processor_count * 4
-            headline_key = args.workload if args.sampler == "Independent" else f"{args.workload}:{args.sampler}"
-            # every configuration whose kernels the counter passes see: the headline at the timed spp, the others at PMC_SPP
-            pmc_configs = [{"key": headline_key, "workload": args.workload, "spp": spp, "sampler": args.sampler, "variant": variant, "scheduler": args.scheduler}]
-            extra, extra_state = [], {}
-            if world == 1 and not args.no_extra and args.workload == "c2" and args.spp is None and args.sampler == "Independent":
-                # Every other BASELINE configuration AT ITS STATED SIZE on this GPU (round 4; round 3 timed them at reduced spp), each with
-                # its own oracle leg on a bounded sample and the parity of the device against it: C1 = configs[0] whole (+ the reference's
-                # own code beside it), C3 at 4096 spp, C4 = the 8-GPU configuration's 1-GPU number at 1024 spp, C5 at 2048 of its 65 536 spp
-                # (>= 1024; the Independent sampler's throughput is spp-invariant beyond the item drain), and C2
-                # once more with the sampler class + filter the reference's converter writes for the README scenes
-                # (tools/tungsten2luisa.py:373-412 there: a low-discrepancy sampler, Gaussian r = 1 -- the stand-in's filter already).
-                # (workload, timed steps, spp (None = the configuration's), seconds of oracle, whole configuration on the CPU, sampler)
-                for w, steps, spp_o, cpu_s, whole, sampler in (("c1", 3, None, 30.0, True, "Independent"), ("c3", 1, None, 8.0, False, "Independent"),
-                                                               ("c4", 1, None, 10.0, False, "Independent"), ("c5", 1, BENCH_SPP_CAP["c5"], 8.0, False, "Independent"),
-                                                               ("c2", 1, None, 8.0, False, "PaddedSobol")):  # (round 5: the low-discrepancy line has its own oracle leg and parity)
-                    v, ms, kms, var, sc, r, sp, d = run_workload(w, args, rank, world, local_rank, tmp, steps, 1, spp_o, sampler, warmup_spp=None if w in ("c1", "c5") else 8)  # (C5: wavefront mode sizes its queues by the frame's spp -- a warm-up on fewer samples leaves a 76-89 GB allocation inside the timed step)
-                    e = {"workload": d, "sampler": sampler, "spp_timed": sp, "spp_config": WORKLOADS[w][2], "value": v, "unit": "Msamples/s", "steps": steps, "ms_per_step": ms,
-                         "kernel_ms": kms, "kernel": kernel_name(var), "algorithmic_bytes_per_sample": ALGORITHMIC_BYTES_PER_SAMPLE[w]}
-                    if cpu_s > 0.0 and not args.no_cpu_baseline:
-                        e["cpu_baseline"], e["algorithmic_bytes_per_sample"], _, (cpu_frame, cpu_spp) = cpu_baseline(sc, r, cpu_s, full_spp=sp if whole else None)
-                        e["parity"] = device_parity(sc, local_rank, cpu_frame, cpu_spp)
-                    else:
-                        e["parity"] = None
-                    if whole and not args.no_cpu_baseline:  # BASELINE configs[0]: Cornell Box 512x512, 64 spp, depth 8 on the CPU -- the whole configuration --
-                        # and the REFERENCE'S OWN code beside it (oracle/_ref, a bounded sample of the same frame); absent where oracle/_ref was not built
-                        ref = reference_leg("c1", r, sp, sampler, 10.0)
-                        if ref is not None:
-                            e["cpu_reference"] = ref
-                    key = w if sampler == "Independent" else f"{w}:{sampler}"
-                    pmc_spp = min(sp, PMC_SPP.get(key, sp))
-                    if not args.no_stats:
-                        extra_state[key] = path_statistics(sc, local_rank, pmc_spp)
-                    pmc_configs.append({"key": key, "workload": w, "spp": pmc_spp, "sampler": sampler, "variant": var, "scheduler": "auto"})
-                    e["_key"] = key
-                    e["_variant"] = var
-                    e["_samples"] = r[0] * r[1] * sp
-                    extra.append(e)
-            # the reference's own code beside the HEADLINE number too (round 6): MegaPath::Li of oracle/_ref on the bench's own C2 description
-            # (InlineMesh form: the same instances, transforms and materials), one process per host thread, a bounded time
-            if world == 1 and not args.no_cpu_baseline and args.workload == "c2":
-                ref = reference_leg("c2", res, spp, args.sampler, 12.0)
-                if ref is not None:
-                    out["cpu_reference"] = ref
-            pmc_all = {}
-            if world == 1 and not args.no_pmc:
-                pmc_all = live_pmc(pmc_configs)
+            if args.full:
+                bytes_per_sample = ALGORITHMIC_BYTES_PER_SAMPLE[args.workload]
+                if world == 1 and not args.no_cpu_baseline:  # the CPU leg runs on rank 0 at N = 1 only
+                    cpu, bytes_per_sample, _, (cpu_frame, cpu_spp) = cpu_baseline(scene, res, args.cpu_seconds)
+                    out["cpu_baseline"] = cpu
+                    out["parity"] = device_parity(scene, local_rank, cpu_frame, cpu_spp, args.scheduler)
+                if world == 1 and not args.no_stats:
+                    stats = path_statistics(scene, local_rank, spp, args.scheduler)
+                    out["rays_per_s"] = value * 1e6 * stats["rays_per_sample"]
+                    out["mean_path_length"] = stats["mean_path_length"]
+                    out["path_statistics"] = stats
+                # one launch renders this rank's shard: samples_per_step / world samples
+                launch_samples = samples_per_step / world
+                import torch
+                simds = torch.cuda.get_device_properties(local_rank).multi_processor_count * 4
+                headline_key = args.workload if args.sampler == "Independent" else f"{args.workload}:{args.sampler}"
+                # every configuration whose kernels the counter passes see: the headline at the timed spp, the others at PMC_SPP
+                pmc_configs = [{"key": headline_key, "workload": args.workload, "spp": spp, "sampler": args.sampler, "variant": variant, "scheduler": args.scheduler}]
+                extra, extra_state = [], {}
+                if world == 1 and not args.no_extra and args.workload == "c2" and args.spp is None and args.sampler == "Independent":
+                    # Every other BASELINE configuration AT ITS STATED SIZE on this GPU (round 4; round 3 timed them at reduced spp), each with
+                    # its own oracle leg on a bounded sample and the parity of the device against it: C1 = configs[0] whole (+ the reference's
+                    # own code beside it), C3 at 4096 spp, C4 = the 8-GPU configuration's 1-GPU number at 1024 spp, C5 at 2048 of its 65 536 spp
+                    # (>= 1024; the Independent sampler's throughput is spp-invariant beyond the item drain), and C2
+                    # once more with the sampler class + filter the reference's converter writes for the README scenes
+                    # (tools/tungsten2luisa.py:373-412 there: a low-discrepancy sampler, Gaussian r = 1 -- the stand-in's filter already).
+                    # (workload, timed steps, spp (None = the configuration's), seconds of oracle, whole configuration on the CPU, sampler)
+                    for w, steps, spp_o, cpu_s, whole, sampler in (("c1", 3, None, 30.0, True, "Independent"), ("c3", 1, None, 8.0, False, "Independent"),
+                                                                   ("c4", 1, None, 10.0, False, "Independent"), ("c5", 1, BENCH_SPP_CAP["c5"], 8.0, False, "Independent"),
+                                                                   ("c2", 1, None, 8.0, False, "PaddedSobol")):  # (round 5: the low-discrepancy line has its own oracle leg and parity)
+                        v, ms, kms, var, sc, r, sp, d = run_workload(w, args, rank, world, local_rank, tmp, steps, 1, spp_o, sampler, warmup_spp=None if w in ("c1", "c5") else 8)  # (C5: wavefront mode sizes its queues by the frame's spp -- a warm-up on fewer samples leaves a 76-89 GB allocation inside the timed step)
+                        e = {"workload": d, "sampler": sampler, "spp_timed": sp, "spp_config": WORKLOADS[w][2], "value": v, "unit": "Msamples/s", "steps": steps, "ms_per_step": ms,
+                             "kernel_ms": kms, "kernel": kernel_name(var), "algorithmic_bytes_per_sample": ALGORITHMIC_BYTES_PER_SAMPLE[w]}
+                        if cpu_s > 0.0 and not args.no_cpu_baseline:
+                            e["cpu_baseline"], e["algorithmic_bytes_per_sample"], _, (cpu_frame, cpu_spp) = cpu_baseline(sc, r, cpu_s, full_spp=sp if whole else None)
+                            e["parity"] = device_parity(sc, local_rank, cpu_frame, cpu_spp)
+                        else:
+                            e["parity"] = None
+                        if whole and not args.no_cpu_baseline:  # BASELINE configs[0]: Cornell Box 512x512, 64 spp, depth 8 on the CPU -- the whole configuration --
+                            # and the REFERENCE'S OWN code beside it (oracle/_ref, a bounded sample of the same frame); absent where oracle/_ref was not built
+                            ref = reference_leg("c1", r, sp, sampler, 10.0)
+                            if ref is not None:
+                                e["cpu_reference"] = ref
+                        key = w if sampler == "Independent" else f"{w}:{sampler}"
+                        pmc_spp = min(sp, PMC_SPP.get(key, sp))
+                        if not args.no_stats:
+                            extra_state[key] = path_statistics(sc, local_rank, pmc_spp)
+                        pmc_configs.append({"key": key, "workload": w, "spp": pmc_spp, "sampler": sampler, "variant": var, "scheduler": "auto"})
+                        e["_key"] = key
+                        e["_variant"] = var
+                        e["_samples"] = r[0] * r[1] * sp
+                        extra.append(e)
+                # the reference's own code beside the HEADLINE number too (round 6): MegaPath::Li of oracle/_ref on the bench's own C2 description
+                # (InlineMesh form: the same instances, transforms and materials), one process per host thread, a bounded time
+                if world == 1 and not args.no_cpu_baseline and args.workload == "c2":
+                    ref = reference_leg("c2", res, spp, args.sampler, 12.0)
+                    if ref is not None:
+                        out["cpu_reference"] = ref
+                pmc_all = {}
+                if world == 1 and not args.no_pmc:
+                    pmc_all = live_pmc(pmc_configs)
 
-            def pmc_of(key, timed_spp):
-                p = pmc_all.get(key)
-                if p is None or "hbm_bytes_per_sample" not in p:
-                    return None, None
-                src = (f"live: rocprofv3 --pmc passes of this run ({', '.join(n for n, _ in PMC_PASSES)}), the same frame at {p['spp']} spp"
-                       + ("" if p["spp"] == timed_spp else f" (per-sample counters x the timed launch's samples; the frame is timed at {timed_spp} spp)"))
-                return p, src
+                def pmc_of(key, timed_spp):
+                    p = pmc_all.get(key)
+                    if p is None or "hbm_bytes_per_sample" not in p:
+                        return None, None
+                    src = (f"live: rocprofv3 --pmc passes of this run ({', '.join(n for n, _ in PMC_PASSES)}), the same frame at {p['spp']} spp"
+                           + ("" if p["spp"] == timed_spp else f" (per-sample counters x the timed launch's samples; the frame is timed at {timed_spp} spp)"))
+                    return p, src
 
-            pmc, pmc_source = pmc_of(headline_key, spp)
-            if pmc is None:
-                prof = os.path.join(ROOT, "profiles", f"pmc_{args.workload}.json")
-                if os.path.exists(prof):
-                    try:
-                        p = json.load(open(prof))
-                        if p.get("source_hash") == source_hash() and p.get("hbm_bytes_per_sample"):  # a profile of another build is not evidence
-                            p.setdefault("valu_wave_instr_per_sample", p.get("valu_wave_instructions_per_sample"))
-                            pmc, pmc_source = p, f"profiles/pmc_{args.workload}.json (same source hash)"
-                    except Exception:
-                        pass
-            # (a scheduler override reaches the counting and parity renders as well: ADVICE r05)
-            out["roofline"] = roofline_block(args.workload, variant, mean_kernel_ms, launch_samples, bytes_per_sample, pmc, pmc_source, out.get("path_statistics"), simds)
-            for e in extra:
-                key, var, n = e.pop("_key"), e.pop("_variant"), e.pop("_samples")
-                p, src = pmc_of(key, e["spp_timed"])
-                e["roofline"] = roofline_block(key.split(":")[0], var, e["kernel_ms"], n, e["algorithmic_bytes_per_sample"], p, src, extra_state.get(key), simds)
-            if extra:
-                out["extra_configs"] = extra
-            if multi_extra:
-                out["extra_configs"] = out.get("extra_configs", []) + multi_extra
+                pmc, pmc_source = pmc_of(headline_key, spp)
+                if pmc is None:
+                    prof = os.path.join(ROOT, "profiles", f"pmc_{args.workload}.json")
+                    if os.path.exists(prof):
+                        try:
+                            p = json.load(open(prof))
+                            if p.get("source_hash") == source_hash() and p.get("hbm_bytes_per_sample"):  # a profile of another build is not evidence
+                                p.setdefault("valu_wave_instr_per_sample", p.get("valu_wave_instructions_per_sample"))
+                                pmc, pmc_source = p, f"profiles/pmc_{args.workload}.json (same source hash)"
+                        except Exception:
+                            pass
+                # (a scheduler override reaches the counting and parity renders as well: ADVICE r05)
+                out["roofline"] = roofline_block(args.workload, variant, mean_kernel_ms, launch_samples, bytes_per_sample, pmc, pmc_source, out.get("path_statistics"), simds)
+                for e in extra:
+                    key, var, n = e.pop("_key"), e.pop("_variant"), e.pop("_samples")
+                    p, src = pmc_of(key, e["spp_timed"])
+                    e["roofline"] = roofline_block(key.split(":")[0], var, e["kernel_ms"], n, e["algorithmic_bytes_per_sample"], p, src, extra_state.get(key), simds)
+                if extra:
+                    out["extra_configs"] = extra
+                if multi_extra:
+                    out["extra_configs"] = out.get("extra_configs", []) + multi_extra
             out["source_hash"] = source_hash()  # the kernel + BVH-builder sources this line was measured on (profiles/*.json carry the same)
+            if args.dump_outputs is not None:
+                dump_outputs(args.dump_outputs, {"film": film})
             print(json.dumps(out), flush=True)
     if dist.is_initialized():
         dist.barrier()

@@ -163,7 +163,7 @@ def test_bench_multi_gpu_path_runs_as_the_driver_launches_it(tmp_path):
     import sys
     env = dict(os.environ, LR_BENCH_FORCE_COLLECTIVE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29517",
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "c1", "--spp", "8",
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "c1", "--spp", "8", "--full",
            "--no-cpu-baseline", "--no-pmc", "--no-stats", "--extra-spp", "4"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -181,3 +181,42 @@ def test_bench_multi_gpu_path_runs_as_the_driver_launches_it(tmp_path):
         assert e["multi_gpu"]["reduced_film_equals_1gpu_render"] is True and e["multi_gpu"]["checked_sample_counts_ok"] is True, e["multi_gpu"]
         assert e["multi_gpu"]["reduce_bytes"] == res[0] * res[1] * 16 and e["multi_gpu"]["rccl_saw_all_ranks"] is True, e["multi_gpu"]
     assert extra["Kitchen"]["kernel"].startswith("lrd::megapool_kernel<5")  # the wavefront camera pass of the pool family
+
+
+def test_dumped_outputs_are_float32_within_the_cap_and_the_same_sample_every_run(tmp_path):
+    """--dump-outputs: a film within the cap is written whole; a larger one keeps a seeded sample of its pixels, the same in every run."""
+    import numpy as np
+    bench = _bench_module()
+    small = np.arange(8 * 6 * 4, dtype=np.float32).reshape(8, 6, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"film": small})
+    assert np.array_equal(np.load(tmp_path / "a" / "film.npy"), small)
+    big = np.random.default_rng(1).random((2160, 3840, 4), dtype=np.float32)  # C4's film: 127 MiB
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"film": big})
+    b, c = np.load(tmp_path / "b" / "film.npy"), np.load(tmp_path / "c" / "film.npy")
+    assert b.dtype == np.float32 and b.nbytes <= bench.DUMP_LIMIT_BYTES and b.shape[1] == 4 and b.shape[0] > big.shape[0] * big.shape[1] // 3
+    assert np.array_equal(b, c)
+    assert np.isin(b[:, 0], big[..., 0]).all()  # pixels of the film, not anything else
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_times_the_steps_it_is_given_and_dumps_the_last_film(tmp_path):
+    """A plain run (no --full) prints the contract's fields for exactly --steps timed steps and nothing that takes runs of its own;
+    --dump-outputs writes the last timed step's film."""
+    import subprocess
+    import sys
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "c1", "--spp", "8",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    bench = _bench_module()
+    assert line["metric"] == bench.METRIC and line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 3 and line["ms_per_step"] > 0.0
+    assert abs(line["value"] - 512 * 512 * 8 / (line["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * line["value"]
+    for key in ("cpu_baseline", "parity", "path_statistics", "roofline", "extra_configs", "cpu_reference", "multi_gpu"):
+        assert key not in line, key
+    film = np.load(tmp_path / "film.npy")
+    assert film.dtype == np.float32 and film.shape == (512, 512, 4) and np.isfinite(film).all()
+    assert (film[..., 3] == 8.0).all() and film[..., :3].sum() > 0.0
