@@ -223,8 +223,19 @@ typedef enum lr_integrator_kind {
     LR_INTEGRATOR_MEGAPATH = 0, /* src/integrators/mega_path.cpp (the hot path)                                  */
     LR_INTEGRATOR_DIRECT = 1,   /* src/integrators/direct.cpp:66-200: one bounce, light / surface / both sampling  */
     LR_INTEGRATOR_NORMAL = 2,   /* src/integrators/normal.cpp:36-70: geometric / shading normal visualiser         */
-    LR_INTEGRATOR_VPT_NAIVE = 3 /* src/integrators/mega_vpt_naive.cpp:68-483: volumetric megakernel  */
+    LR_INTEGRATOR_VPT_NAIVE = 3,/* src/integrators/mega_vpt_naive.cpp:68-483: volumetric megakernel  */
+    LR_INTEGRATOR_AOV = 4       /* src/integrators/aov.cpp:237-366: auxiliary buffers (lrhip_aov_download)           */
 } lr_integrator_kind;
+/* AOV components (aov.cpp:19-28): bit k of lr_integrator.flags enables component k.  Channels per pixel: sample, diffuse, specular,
+ * normal, albedo 3; depth 1; roughness 3 (rx, ry, 0: aov.cpp:157 widens 2 to 3); ndc 3; mask 1 */
+enum {
+    LR_AOV_SAMPLE = 0, LR_AOV_DIFFUSE = 1, LR_AOV_SPECULAR = 2, LR_AOV_NORMAL = 3, LR_AOV_ALBEDO = 4,
+    LR_AOV_DEPTH = 5, LR_AOV_ROUGHNESS = 6, LR_AOV_NDC = 7, LR_AOV_MASK = 8, LR_AOV_COMPONENTS = 9
+};
+#define LR_AOV_BIT(component) (1u << (component))
+#define LR_AOV_ALL 0x1ffu
+/* aov.cpp:33-37: which sample counts write files */
+enum { LR_AOV_DUMP_POWER2 = 0, LR_AOV_DUMP_ALL = 1, LR_AOV_DUMP_FINAL = 2 };
 enum {
     LR_DIRECT_SAMPLE_LIGHTS = 1u,   /* importance_sampling "light" | "both"   (direct.cpp:27-42) */
     LR_DIRECT_SAMPLE_SURFACES = 2u, /* importance_sampling "surface" | "both"                    */
@@ -239,7 +250,7 @@ typedef struct lr_integrator {
     float env_prob;       /* UniformLightSampler::_env_prob, uniform.cpp:39-48 */
     uint32_t light_count; /* pipeline.lights().size(): number of distinct Light nodes, uniform.cpp:82 */
     uint32_t kind;        /* lr_integrator_kind */
-    uint32_t flags;       /* LR_DIRECT_* / LR_NORMAL_* */
+    uint32_t flags;       /* LR_DIRECT_* / LR_NORMAL_* / LR_AOV_BIT(LR_AOV_*) */
     uint32_t environment_medium_tag; /* Pipeline::environment_medium_tag (pipeline.cpp:77-79); LR_INVALID_ID = none */
 } lr_integrator;
 

@@ -115,6 +115,12 @@ int lrhip_synchronize(lrhip_ctx *ctx);
  * converted == 0: the raw (sum r, sum g, sum b, n) film.  Synchronises.              */
 int lrhip_film_download(lrhip_ctx *ctx, float *rgba, int converted);
 
+/* The AOV integrator (LR_INTEGRATOR_AOV, src/integrators/aov.cpp): the raw per-pixel sums of one component (LR_AOV_*, lr_scene.h),
+ * W x H x channels floats, row 0 at the top, channels interleaved (3 for every component but depth and mask; roughness is (rx, ry, 0)).
+ * Divide by the sample count for the reference's images.  The buffers of the enabled components are allocated by lrhip_upload_scene
+ * and cleared with the film by lrhip_film_clear; an AOV scene leaves the film itself untouched.  Synchronises.               */
+int lrhip_aov_download(lrhip_ctx *ctx, uint32_t component, float *out);
+
 /* The path's only collective: sum-reduce of the per-rank films to rank `root` over RCCL / xGMI, in place on the film
  * this context accumulates into, in stream order behind the renders.  `nccl_comm` is the caller's ncclComm_t (one per process /
  * GPU, created by the caller: ncclCommInitRank); librccl.so is loaded on first use, so the library has no link-time dependency
@@ -158,6 +164,7 @@ double lrhip_last_render_ms(lrhip_ctx *ctx);
 #define LRHIP_FEAT_AUX_INTEGRATORS 128u
 #define LRHIP_FEAT_VOLUMETRIC 256u
 #define LRHIP_FEAT_NESTED 512u /* Mix trees with Layered leaves / Layered surfaces with Mix interfaces */
+#define LRHIP_FEAT_AOV 32768u  /* the AOV integrator's kernels (lrhip_last_variant: with the all-closures scene bits) */
 uint32_t lrhip_last_variant(lrhip_ctx *ctx);
 
 /* Diagnostics of ONE context, for tests and tools (the product path never calls it; the library reads no environment variable):

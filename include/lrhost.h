@@ -48,9 +48,15 @@ int lrhost_scene_camera_count(const lrhost_scene *scene);
 int lrhost_scene_view(const lrhost_scene *scene, int camera_index, lr_scene *out);
 const char *lrhost_scene_camera_file(const lrhost_scene *scene, int camera_index);
 int lrhost_scene_has_lighting(const lrhost_scene *scene);
+/* The AOV integrator (lr_integrator.kind == LR_INTEGRATOR_AOV, components in lr_integrator.flags; src/integrators/aov.cpp:48-87):
+ * noisy_count (samples per pixel, in place of the camera's spp; at least 8) and the dump strategy (LR_AOV_DUMP_*).  An error for
+ * any other integrator. */
+int lrhost_scene_aov_settings(const lrhost_scene *scene, uint32_t *noisy_count, uint32_t *dump);
 void lrhost_scene_destroy(lrhost_scene *scene);
 
 int lrhost_save_image(const char *path, const float *rgba, uint32_t width, uint32_t height);
+/* the same for 1 (HDR: gray; EXR: one channel named "A"), 3 (RGB) or 4 interleaved float channels per pixel */
+int lrhost_save_image_channels(const char *path, const float *pixels, uint32_t width, uint32_t height, uint32_t channels);
 /* load to float RGBA (row 0 = top); caller frees with lrhost_free */
 int lrhost_load_image(const char *path, float **rgba, uint32_t *width, uint32_t *height, uint32_t *channels);
 void lrhost_free(void *p);

@@ -178,6 +178,8 @@ def host_lib() -> C.CDLL:
         lib.lrhost_scene_camera_file.argtypes = [C.c_void_p, C.c_int]
         lib.lrhost_scene_has_lighting.argtypes = [C.c_void_p]
         lib.lrhost_save_image.argtypes = [C.c_char_p, C.c_void_p, u32, u32]
+        lib.lrhost_save_image_channels.argtypes = [C.c_char_p, C.c_void_p, u32, u32, u32]
+        lib.lrhost_scene_aov_settings.argtypes = [C.c_void_p, C.POINTER(u32), C.POINTER(u32)]
         lib._lr_ready = True
     return lib
 
@@ -226,5 +228,6 @@ def hip_lib(path: str | None = None) -> C.CDLL:
         lib.lrhip_set_texture_storage.argtypes = [C.c_void_p, C.c_uint32]
         lib.lrhip_packed_texels.restype = C.c_uint64
         lib.lrhip_packed_texels.argtypes = [C.c_void_p]
+        lib.lrhip_aov_download.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         lib._lr_ready = True
     return lib

@@ -454,4 +454,50 @@ LR_HEAVY HeavySample heavy_sample(const HeavyCtx *cxp, float u_lobe, f2 u_bsdf) 
     return r;
 }
 
+// ---- Surface::Closure::albedo / roughness (the AOV integrator, aov.cpp:276-277 and :360).  Roughness is
+// TrowbridgeReitzDistribution::alpha_to_roughness = sqrt(max(alpha, 1e-4)) (scattering.cpp:141-143) of the closure's distribution:
+// Mirror / Glass / Plastic / Metal their alpha, Disney its DisneyMicrofacetDistribution (dev_bsdf.h: disney_lobes); Matte (1, 1).
+LR_D void closure_albedo_roughness(const DClosure &c, f3 &albedo, f2 &roughness) {
+    auto r = [](float a) { return sqrtf(fmaxf(a, 1e-4f)); };
+    albedo = mk3(c.c0[0], c.c0[1], c.c0[2]);// Matte Kd, Mirror refl, Glass Kr, Plastic Kd (its populate_closure's), Disney color
+    roughness = f2{r(c.alpha_x), r(c.alpha_y)};
+    if (c.kind == LR_SURFACE_MATTE) { roughness = f2{1.f, 1.f}; }// matte.cpp:70-71
+    else if (c.kind == LR_SURFACE_METAL) {// metal.cpp:220-224: fresnel_conductor(1, 1, n, k) * refl
+        albedo = fresnel_conductor(1.f, 1.f, mk3(c.c0[0], c.c0[1], c.c0[2]), mk3(c.c1[0], c.c1[1], c.c1[2])) * mk3(c.c2[0], c.c2[1], c.c2[2]);
+    } else if (c.kind == LR_SURFACE_DISNEY) {// disney.cpp:527-530 / :778-782
+        const auto aspect = sqrtf(1.f - c.e[kDisneyAnisotropic] * .9f);
+        roughness = f2{r(fmaxf(0.001f, c.e[kDisneyRoughness] / aspect)), r(fmaxf(0.001f, c.e[kDisneyRoughness] * aspect))};
+    }
+}
+// ... of a Disney / Mix / Layered surface, out of line like heavy_evaluate / heavy_sample.  Mix: albedo a * r + b * (1 - r), roughness
+// lerp(b, a, r) (mix.cpp:124-138); Layered: its top interface's (layered.cpp:242-243).  The AOV kernels reject nested Mix / Layered
+// surfaces (lrhip_upload_scene), so the children here are basic or Disney closures.
+template<bool MIX, bool LAYERED>
+LR_HEAVY void heavy_albedo_roughness(const HeavyCtx *cxp, f3 *albedo, f2 *roughness) {
+    auto &cx = *cxp;
+    auto &c = cx.closure;
+    if (MIX && c.kind == LR_SURFACE_MIX) {
+        f3 a[2];
+        f2 r[2];
+        for (auto k = 0u; k < 2u; k++) {
+            DClosure child;
+            Frame fr;
+            load_lobe(cx.tb, cx.uv, cx.ng, cx.wo, c.x[k], cx.shading, child, fr);
+            closure_albedo_roughness(child, a[k], r[k]);
+        }
+        const auto ratio = c.s0;
+        *albedo = a[0] * ratio + a[1] * (1.f - ratio);
+        *roughness = f2{lerp(r[1].x, r[0].x, ratio), lerp(r[1].y, r[0].y, ratio)};
+        return;
+    }
+    if (LAYERED && c.kind == LR_SURFACE_LAYERED) {
+        DClosure top;
+        Frame fr;
+        load_lobe(cx.tb, cx.uv, cx.ng, cx.wo, c.x[0], cx.shading, top, fr);
+        closure_albedo_roughness(top, *albedo, *roughness);
+        return;
+    }
+    closure_albedo_roughness(c, *albedo, *roughness);// Disney
+}
+
 }// namespace lrd

@@ -206,6 +206,13 @@ struct DScene {
     const uint64_t *vdc_bytes, *vdc_inv_bytes;// [7][256]: their products with every value of every byte (Sobol sampler, scale > 1)
     const DEnvironment *env;
     WfArgs wf;// wavefront mode only (behind the scene pointer like everything else: scalar loads where a field is used)
+    // the AOV integrator (kFeatAov variants only; appended, so no other field moves): planar sums [channel][pixel] of the enabled
+    // components, their partial planes [chunk][channel][pixel] when a launch has several chunks, and each component's first channel
+    // (LR_AOV_* bit order; kInvalid = not enabled)
+    float *aov;
+    float *aov_partial;
+    uint32_t aov_channels;
+    uint32_t aov_offset[LR_AOV_COMPONENTS];
 };
 
 // The scene record reaches the kernels through a pointer into constant memory, not by value: as a 400-byte kernel argument

@@ -30,6 +30,9 @@ enum : uint32_t {
     // exists and the scene's sampler is PaddedSobol, the run-time generic kernel of the same mask otherwise.  C2: 953 -> 975 Msamples/s at
     // 256 spp, films bit-identical (profiles/r06y_padded_sobol_kernels.txt)
     kFeatPadded = 16384u,
+    // the AOV integrator (src/integrators/aov.cpp): auxiliary buffers summed per wave in LDS (dev_wavefront.h: aov_add), on top of the
+    // all-closures scene mask only; the one-path-per-lane kernel with a second throughput / radiance for the diffuse split, no Russian roulette
+    kFeatAov = 32768u,
     kFeatSceneMask = kFeatEnv | kFeatAlpha | kFeatDisney | kFeatMix | kFeatLayered
 };
 
@@ -44,6 +47,16 @@ LR_D void film_accumulate(float4 *pixel, f3 rgb, float clamp) {
         }
         atomicAdd(&pixel->w, 1.f);
     }
+}
+
+// AuxiliaryBuffer::accumulate (aov.cpp:190-199) into the wave's LDS copy of its tile: channel c of pixel `pix` at tile[c * 64 + pix]
+// (a component's channels from scene.aov_offset[component]; kInvalid = not enabled).  A value with a NaN component is skipped; unlike
+// the film, infinities are added and nothing is clamped.
+LR_D void aov_add(const DScene &scene, float *tile, uint32_t component, uint32_t pix, f3 v, uint32_t channels) {
+    const auto off = scene.aov_offset[component];
+    if (off == kInvalid || isnan(v.x) || (channels > 1u && (isnan(v.y) || isnan(v.z)))) { return; }
+    atomicAdd(tile + off * 64u + pix, v.x);
+    if (channels > 1u) { atomicAdd(tile + (off + 1u) * 64u + pix, v.y), atomicAdd(tile + (off + 2u) * 64u + pix, v.z); }
 }
 
 // Radiance -> 64-bit FIXED POINT (two's complement in an unsigned word: sums wrap exactly, so negative samples -- the Mitchell and

@@ -23,6 +23,21 @@ __global__ void resolve_partial_kernel(float4 *film, const float4 *partial, uint
     film[i] = v;
 }
 
+// the AOV integrator: aov[c][pixel] += sum over chunks of partial[chunk][c][pixel], in chunk order (deterministic)
+__global__ void resolve_aov_partial_kernel(float *aov, const float *partial, uint32_t pixel_count, uint32_t channels, uint32_t chunk_count,
+                                           uint32_t width, uint32_t tiles_x, uint32_t tile_begin, uint32_t tile_end, uint32_t tile_stride) {
+    const auto n = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (n >= static_cast<size_t>(pixel_count) * channels) { return; }
+    const auto i = static_cast<uint32_t>(n % pixel_count), c = static_cast<uint32_t>(n / pixel_count);
+    auto px = i % width, py = i / width;
+    auto ty = py / 8u, tcol = px / 8u;
+    auto tile = ty * tiles_x + (tcol + tiles_x - ty % tiles_x) % tiles_x;// (resolve_partial_kernel)
+    if (tile < tile_begin || tile >= tile_end || (tile - tile_begin) % tile_stride != 0u) { return; }
+    auto v = aov[n];
+    for (auto k = 0u; k < chunk_count; k++) { v += partial[(static_cast<size_t>(k) * channels + c) * pixel_count + i]; }
+    aov[n] = v;
+}
+
 // wavefront mode: the fixed-point radiance sums of the paths that finished outside their tile's wave (dev_wavefront.h:
 // wf_film_accumulate) join the film once per lrhip_render, and the sums are cleared for the next call
 __global__ void wf_resolve_kernel(float4 *film, unsigned long long *accum, uint32_t pixel_count, double inv_scale) {

@@ -39,6 +39,12 @@ LR_PADDED_LIST(LR_DECLARE_VARIANT)
     extern "C" __attribute__((weak)) hipError_t lrhip_heavy_occupancy_##mask(int *);
 LR_HEAVY_LIST(LR_HEAVY_DECL)
 #undef LR_HEAVY_DECL
+// the AOV integrator's kernels (variants.h: LR_AOV_LIST): their launch takes the dynamic LDS of the enabled channels
+#define LR_AOV_DECL(mask)                                                                                                     \
+    extern "C" __attribute__((weak)) hipError_t lrhip_aov_launch_##mask(unsigned, hipStream_t, const lrd::DScene *, const lrd::RenderArgs *, unsigned); \
+    extern "C" __attribute__((weak)) hipError_t lrhip_aov_occupancy_##mask(int *, unsigned);
+LR_AOV_LIST(LR_AOV_DECL)
+#undef LR_AOV_DECL
 
 namespace {
 
@@ -59,6 +65,17 @@ static_assert(sizeof(kVariants) / sizeof(kVariants[0]) == lrd::kSceneVariantCoun
 #define LR_HEAVY_ENTRY(mask) VariantEntry{mask##u, lrhip_heavy_launch_##mask, lrhip_heavy_occupancy_##mask},
 const VariantEntry kHeavyVariants[] = {LR_HEAVY_LIST(LR_HEAVY_ENTRY)};
 #undef LR_HEAVY_ENTRY
+struct AovEntry {
+    uint32_t mask;
+    hipError_t (*launch)(unsigned, hipStream_t, const lrd::DScene *, const lrd::RenderArgs *, unsigned);
+    hipError_t (*occupancy)(int *, unsigned);
+};
+#define LR_AOV_ENTRY(mask) AovEntry{mask##u, lrhip_aov_launch_##mask, lrhip_aov_occupancy_##mask},
+const AovEntry kAovVariants[] = {LR_AOV_LIST(LR_AOV_ENTRY)};
+#undef LR_AOV_ENTRY
+constexpr size_t kAovVariantCount = sizeof(kAovVariants) / sizeof(kAovVariants[0]);
+// channels per pixel of each AOV component (lr_scene.h: LR_AOV_*)
+constexpr uint32_t kAovChannels[LR_AOV_COMPONENTS] = {3u, 3u, 3u, 3u, 3u, 1u, 3u, 3u, 1u};
 int find_variant(const VariantEntry *table, size_t n, uint32_t mask) {
     for (size_t k = 0; k < n; k++) {
         if (table[k].mask == mask) { return static_cast<int>(k); }
@@ -162,6 +179,9 @@ struct lrhip_ctx {
     // round 4: the path-pool scheduler (megapool_kernel.h): slot records of every resident wave; lrhip_set_scheduler
     DeviceBuffer pool;
     uint32_t scheduler{0u};      // lrhip_set_scheduler: 0 = automatic (wants_pool below), 1 = one path per lane, 2 = the pool kernels where one exists for the scene
+    // the AOV integrator: planar sums [channel][pixel] of the enabled components (lrd::DScene::aov) and the chunks' partial planes
+    DeviceBuffer aov, aov_partial;
+    int aov_blocks[kAovVariantCount];// resident blocks per CU of each AOV kernel at the uploaded scene's LDS size (-1: not asked yet)
 };
 
 namespace {
@@ -395,6 +415,7 @@ void lrhip_destroy(lrhip_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     release_scene(ctx);
     ctx->film_own.release(), ctx->converted.release(), ctx->partial.release();
+    ctx->aov.release(), ctx->aov_partial.release();
     ctx->spill.release(), ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->wf_counts.release(), ctx->wf_accum.release(), ctx->pool.release(), ctx->counters.release(), ctx->work_counter.release(), ctx->scene_record.release();
     if (ctx->ev_begin) { (void)hipEventDestroy(ctx->ev_begin); }
     if (ctx->ev_end) { (void)hipEventDestroy(ctx->ev_end); }
@@ -885,7 +906,7 @@ int lrhip_upload_scene(lrhip_ctx *ctx, const lr_scene *s) {
     }
     d.max_depth = s->integrator.max_depth, d.rr_depth = s->integrator.rr_depth;
     d.integrator_kind = s->integrator.kind, d.integrator_flags = s->integrator.flags;
-    if (s->integrator.kind > LR_INTEGRATOR_VPT_NAIVE) { release_scene(ctx); return fail(LRHIP_ERROR_UNSUPPORTED, "lrhip_upload_scene: unknown integrator kind"); }
+    if (s->integrator.kind > LR_INTEGRATOR_AOV) { release_scene(ctx); return fail(LRHIP_ERROR_UNSUPPORTED, "lrhip_upload_scene: unknown integrator kind"); }
     d.env_medium_tag = s->integrator.environment_medium_tag;
     const auto nested = (ctx->features & lrd::kFeatNest) != 0u;
     if (s->integrator.kind == LR_INTEGRATOR_VPT_NAIVE) {// the volumetric megakernel is one kernel with everything in it
@@ -899,6 +920,9 @@ int lrhip_upload_scene(lrhip_ctx *ctx, const lr_scene *s) {
         if (auto r = upload(ctx, s->media, s->medium_count, &d.media); r != LRHIP_OK) { release_scene(ctx); return r; }
         ctx->features = lrd::kFeatVpt;
         if (nested) { release_scene(ctx); return fail(LRHIP_ERROR_UNSUPPORTED, "lrhip_upload_scene: Mix / Layered surfaces nested in each other are supported by the MegaPath integrator only"); }
+    } else if (s->integrator.kind == LR_INTEGRATOR_AOV) {// the AOV integrator has kernels of its own on top of the all-closures mask
+        if (nested) { release_scene(ctx); return fail(LRHIP_ERROR_UNSUPPORTED, "lrhip_upload_scene: Mix / Layered surfaces nested in each other are supported by the MegaPath integrator only"); }
+        ctx->features |= lrd::kFeatSceneMask | lrd::kFeatAov;
     } else if (s->integrator.kind != LR_INTEGRATOR_MEGAPATH) {
         if (nested) { release_scene(ctx); return fail(LRHIP_ERROR_UNSUPPORTED, "lrhip_upload_scene: Mix / Layered surfaces nested in each other are supported by the MegaPath integrator only"); }
         // the sibling integrators (Direct / Normal) live in the all-features variant only
@@ -991,6 +1015,20 @@ int lrhip_upload_scene(lrhip_ctx *ctx, const lr_scene *s) {
         ctx->film = static_cast<float4 *>(ctx->film_own.ptr);
     }
     LR_HIP_CHECK(hipMemset(ctx->film, 0, film_bytes));
+    // the AOV buffers of the enabled components (lr_integrator.flags), in LR_AOV_* order
+    d.aov = nullptr, d.aov_partial = nullptr, d.aov_channels = 0u;
+    for (uint32_t k = 0u; k < LR_AOV_COMPONENTS; k++) {
+        const auto on = s->integrator.kind == LR_INTEGRATOR_AOV && (s->integrator.flags & LR_AOV_BIT(k)) != 0u;
+        d.aov_offset[k] = on ? d.aov_channels : lrd::kInvalid;
+        if (on) { d.aov_channels += kAovChannels[k]; }
+    }
+    if (d.aov_channels != 0u) {
+        const auto aov_bytes = static_cast<size_t>(ctx->width) * ctx->height * d.aov_channels * sizeof(float);
+        if (auto r = ensure(ctx->aov, aov_bytes); r != LRHIP_OK) { return r; }
+        LR_HIP_CHECK(hipMemset(ctx->aov.ptr, 0, aov_bytes));
+        d.aov = static_cast<float *>(ctx->aov.ptr);
+    }
+    for (auto &b : ctx->aov_blocks) { b = -1; }
     // persistent grid: as many blocks as are resident, asked per variant at its first launch (lrhip_render); the
     // traversal-stack overflow area is sized for the densest variant
     for (auto &b : ctx->variant_blocks) { b = -1; }
@@ -1018,6 +1056,9 @@ int lrhip_film_clear(lrhip_ctx *ctx) {
     if (ctx == nullptr || !ctx->scene_ready) { return fail(LRHIP_ERROR_INVALID, "lrhip_film_clear: no scene uploaded"); }
     LR_HIP_CHECK(hipSetDevice(ctx->device));
     LR_HIP_CHECK(hipMemsetAsync(ctx->film, 0, static_cast<size_t>(ctx->width) * ctx->height * sizeof(float4), ctx->stream));
+    if (ctx->scene.aov_channels != 0u) {
+        LR_HIP_CHECK(hipMemsetAsync(ctx->aov.ptr, 0, static_cast<size_t>(ctx->width) * ctx->height * ctx->scene.aov_channels * sizeof(float), ctx->stream));
+    }
     return LRHIP_OK;
 }
 
@@ -1304,10 +1345,54 @@ static int render_wavefront(lrhip_ctx *ctx, const lrhip_render_params *p, uint32
     return LRHIP_OK;
 }
 
+// The AOV integrator's launch (lrhip_render prepared `args`): one kernel of kAovVariants with the wave tiles of the enabled channels in dynamic
+// LDS, and, when the launch has several chunks, the AOV partial planes resolved in chunk order like the film's -- bit-reproducible run to
+// run and under any tile sharding with the same balance_shards.  The film is not touched (aov.cpp accumulates none).
+static int render_aov(lrhip_ctx *ctx, const lrhip_render_params *p, const AovEntry &entry, int &entry_blocks, lrd::RenderArgs &args,
+                      uint32_t chunk_count, uint32_t tiles_x) {
+    const auto pixel_count = ctx->width * ctx->height;
+    const auto channels = ctx->scene.aov_channels;
+    const auto lds_bytes = static_cast<unsigned>(lrd::kWavesPerBlock * 64u * channels * sizeof(float));
+    if (entry_blocks < 0) {
+        int blocks_per_cu = 0;
+        LR_HIP_CHECK(entry.occupancy(&blocks_per_cu, lds_bytes));
+        entry_blocks = std::max(1, std::min(blocks_per_cu, static_cast<int>(kMaxBlocksPerCu)));
+    }
+    const auto resident = ctx->cu_count * static_cast<uint32_t>(entry_blocks);
+    args.total_threads = resident * lrd::kBlockThreads;
+    if (chunk_count > 1u) {
+        if (auto r = ensure(ctx->partial, static_cast<size_t>(chunk_count) * pixel_count * sizeof(float4)); r != LRHIP_OK) { return r; }
+        args.partial = static_cast<float4 *>(ctx->partial.ptr);
+        if (channels != 0u) {
+            if (auto r = ensure(ctx->aov_partial, static_cast<size_t>(chunk_count) * channels * pixel_count * sizeof(float)); r != LRHIP_OK) { return r; }
+        }
+    }
+    ctx->scene.aov_partial = chunk_count > 1u && channels != 0u ? static_cast<float *>(ctx->aov_partial.ptr) : nullptr;
+    ctx->scene.wf.count_at_flush = 0u;
+    const auto blocks = std::min(resident, (args.item_count + 3u) / 4u);
+    if (auto r = ensure(ctx->scene_record, sizeof(lrd::DScene)); r != LRHIP_OK) { return r; }
+    LR_HIP_CHECK(hipMemcpyAsync(ctx->scene_record.ptr, &ctx->scene, sizeof(lrd::DScene), hipMemcpyHostToDevice, ctx->stream));
+    if (!ctx->in_split) { LR_HIP_CHECK(hipEventRecord(ctx->ev_begin, ctx->stream)); }
+    LR_HIP_CHECK(entry.launch(blocks, ctx->stream, static_cast<const lrd::DScene *>(ctx->scene_record.ptr), &args, lds_bytes));
+    ctx->last_variant = entry.mask;
+    LR_HIP_CHECK(hipGetLastError());
+    LR_HIP_CHECK(hipEventRecord(ctx->ev_end, ctx->stream));
+    ctx->timed = true;
+    if (chunk_count > 1u && channels != 0u) {
+        const auto n = static_cast<size_t>(pixel_count) * channels;
+        hipLaunchKernelGGL(lrd::resolve_aov_partial_kernel, dim3(static_cast<unsigned>((n + 255u) / 256u)), dim3(256), 0, ctx->stream,
+                           ctx->scene.aov, ctx->scene.aov_partial, pixel_count, channels, chunk_count, ctx->width, tiles_x, p->tile_begin,
+                           p->tile_end, p->tile_stride);
+        LR_HIP_CHECK(hipGetLastError());
+    }
+    return LRHIP_OK;
+}
+
 // Which of the kernels that sum the film in 64-bit fixed point a call of this scene takes, PROVIDED the sums fit (fixed_point_bits):
 // 1 wavefront mode (render_wavefront), 2 a pool kernel, 0 neither (the float-accumulating kernels of rounds 1-3).  One place for the
 // conditions: lrhip_render decides with it whether a call beyond the fixed-point range is worth rendering in sample sub-ranges.
 static int fixed_point_film_kind(const lrhip_ctx *ctx, bool count, bool generic) {
+    if ((ctx->features & lrd::kFeatAov) != 0u) { return 0; }// (the AOV kernels sum in fp32, like the film of rounds 1-3)
     if (ctx->wf_mode != 1u && ctx->diag_force_features == 0u && !ctx->env_tree && (ctx->features & (lrd::kFeatAux | lrd::kFeatVpt)) == 0u) {
         const auto plain = pick_variant(ctx->features, false, generic, false, ctx->packed_texel_words != 0u);
         if (plain >= 0 && (kVariants[plain].mask & (lrd::kFeatMix | lrd::kFeatLayered)) != 0u) { return 1; }
@@ -1404,13 +1489,25 @@ int lrhip_render(lrhip_ctx *ctx, const lrhip_render_params *p) {
     // anyway hold -- the ones with the Mix interpreter (the auxiliary and volumetric kernels are such variants already)
     if (ctx->env_tree && (features & (lrd::kFeatAux | lrd::kFeatVpt)) == 0u) { features |= lrd::kFeatMix; }
     const auto byte_texels = ctx->packed_texel_words != 0u;// (only a kernel that decodes 8-bit texels will do: pick_variant)
-    auto vi = pick_variant(features, count, generic, false, byte_texels);
+    const auto aov = (ctx->features & lrd::kFeatAov) != 0u;// the AOV integrator: its own kernels (kAovVariants), looked up by mask below
+    auto vi = aov ? -1 : pick_variant(features, count, generic, false, byte_texels);
     // round 4: the path-pool scheduler (megapool_kernel.h) where a pool kernel is compiled for a scene the legacy search would have given
     // a lean kernel (no out-of-line closures, no sibling integrator), and the fixed-point film can hold the frame
     auto pool = false;
     if (wants_pool(ctx) && fixed_bits >= 0 && ctx->scene.max_depth < 65536u && vi >= 0 && (kVariants[vi].mask & (lrd::kFeatMix | lrd::kFeatLayered | lrd::kFeatAux | lrd::kFeatVpt)) == 0u) {
         const auto vp = pick_variant(features, count, generic, true, byte_texels);
         if (vp >= 0 && kVariants[vp].launch != nullptr && kVariants[vp].occupancy != nullptr && (kVariants[vp].mask & lrd::kFeatWf) == 0u) { vi = vp, pool = true; }
+    }
+    if (aov) {
+        const auto mask = lrd::kFeatSceneMask | lrd::kFeatAov | (count ? lrd::kFeatCount : 0u) | (generic ? lrd::kFeatGeneric : 0u);
+        auto ai = -1;
+        for (size_t k = 0; k < kAovVariantCount; k++) {
+            if (kAovVariants[k].mask == mask) { ai = static_cast<int>(k); }
+        }
+        if (ai < 0 || kAovVariants[ai].launch == nullptr || kAovVariants[ai].occupancy == nullptr) {
+            return fail(LRHIP_ERROR_UNSUPPORTED, "lrhip_render: no AOV kernel for feature mask " + std::to_string(mask) + " was compiled into this library");
+        }
+        return render_aov(ctx, p, kAovVariants[ai], ctx->aov_blocks[ai], args, chunk_count, tiles_x);
     }
     if (vi < 0 || kVariants[vi].launch == nullptr || kVariants[vi].occupancy == nullptr) {
         return fail(LRHIP_ERROR_UNSUPPORTED, "lrhip_render: no megakernel variant for feature mask " + std::to_string(ctx->features) +
@@ -1528,6 +1625,22 @@ int lrhip_film_download(lrhip_ctx *ctx, float *rgba, int converted) {
     }
     LR_HIP_CHECK(hipMemcpyAsync(rgba, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     LR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return LRHIP_OK;
+}
+
+int lrhip_aov_download(lrhip_ctx *ctx, uint32_t component, float *out) {
+    if (ctx == nullptr || out == nullptr || !ctx->scene_ready || component >= LR_AOV_COMPONENTS) { return fail(LRHIP_ERROR_INVALID, "lrhip_aov_download: invalid argument"); }
+    const auto off = ctx->scene.aov_offset[component];
+    if (off == lrd::kInvalid) { return fail(LRHIP_ERROR_INVALID, "lrhip_aov_download: the component is not enabled in the uploaded scene"); }
+    LR_HIP_CHECK(hipSetDevice(ctx->device));
+    const auto pixel_count = static_cast<size_t>(ctx->width) * ctx->height;
+    const auto channels = kAovChannels[component];
+    std::vector<float> planes(pixel_count * channels);
+    LR_HIP_CHECK(hipMemcpyAsync(planes.data(), ctx->scene.aov + off * pixel_count, planes.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    LR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < pixel_count; i++) {
+        for (uint32_t c = 0u; c < channels; c++) { out[i * channels + c] = planes[c * pixel_count + i]; }
+    }
     return LRHIP_OK;
 }
 

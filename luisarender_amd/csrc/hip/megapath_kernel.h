@@ -46,6 +46,9 @@ namespace lrd {
 //   kFeatAux      the sibling integrators that reuse this kernel's pieces: DirectLighting
 //                 (src/integrators/direct.cpp:66-200) and NormalVisualizer (normal.cpp:36-70), selected at run time by
 //                 scene.integrator_kind; debug / AOV views, so they only exist on top of the all-features variant
+//   kFeatAov      the AOV integrator (src/integrators/aov.cpp:237-366), also on top of the all-features variant only: a second throughput
+//                 and radiance for the diffuse part, first-hit buffers, no Russian roulette; its sums go to per-wave LDS tiles of the
+//                 enabled channels (dynamic LDS: megapath_variant.hip) and from there to scene.aov like the film's (lrhip_aov_download)
 // the precompiled scene-feature sets, smallest first (each also exists x {Count} x {Generic}); csrc/hip/variants/*.hip
 constexpr uint32_t kSceneVariants[] = {
     0u,
@@ -133,7 +136,9 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
     const DScene &scene = *(const DScene *)scene_ptr;
     constexpr bool COUNT = (F & kFeatCount) != 0u, PCG = (F & kFeatGeneric) != 0u, ENV = (F & kFeatEnv) != 0u,
                    ALPHA = (F & kFeatAlpha) != 0u, DISNEY = (F & kFeatDisney) != 0u, MIX = (F & kFeatMix) != 0u,
-                   LAYERED = (F & kFeatLayered) != 0u, AUX = (F & kFeatAux) != 0u, WF = (F & kFeatWf) != 0u, CONT = (F & kFeatCont) != 0u;
+                   LAYERED = (F & kFeatLayered) != 0u, AUX = (F & kFeatAux) != 0u, WF = (F & kFeatWf) != 0u, CONT = (F & kFeatCont) != 0u,
+                   AOV = (F & kFeatAov) != 0u;
+    static_assert(!AOV || (MIX && LAYERED && !AUX && !WF), "the AOV kernel is the all-closures one-path-per-lane kernel");
     static_assert(!LAYERED || DISNEY, "the Layered interpreter instantiates the Disney closure");
     // (Disney inline in the wavefront kernels, only Mix / Layered parked, was measured: C5 at 512 spp 442 -> 386 Msamples/s -- the lean
     // kernel pays 109 spilled VGPRs for it, profiles/archive/r03i_wavefront_ab.txt)
@@ -151,6 +156,11 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
     TraversalStack stack{s_stack + tid, args.spill + gtid, args.total_threads, s_stage + __builtin_amdgcn_readfirstlane(tid >> 6u) * kStageWave};
     const auto film_tile = s_film + (tid >> 6u) * 64u;
     DCounters local{};
+    float *aov_tile = nullptr;// AOV: this wave's [channel][64] sums (scene.aov_channels channels)
+    if constexpr (AOV) {
+        extern __shared__ float s_aov[];
+        aov_tile = s_aov + (tid >> 6u) * 64u * scene.aov_channels;
+    }
     const auto t_wave = COUNT ? __builtin_readcyclecounter() : 0ull;
 
     // the continuation pass (CONT) works through the records the heavy kernel wrote this round, kWfItemRecords of them per item;
@@ -176,6 +186,9 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
         const auto q_total = CONT ? min(item_records, cont_total - item * item_records) : (s_end > s_begin ? (s_end - s_begin) * 64u : 0u);
         auto q_next = 0u;// wave-uniform
         film_tile[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (AOV) {
+            for (auto c = 0u; c < scene.aov_channels; c++) { aov_tile[c * 64u + lane] = 0.f; }
+        }
         auto px = 0u, py = 0u;
         auto pixel = film_tile;// LDS accumulator of the pixel this lane's current sample belongs to
         auto pixel_index = 0u; // WF: the same pixel in the film (a parked path takes it along)
@@ -188,6 +201,10 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
         auto pdf_bsdf = 1e16f;
         auto depth = 0u;
         auto path_open = false, traced_shadow = false, traced_closest = false;
+        // AOV (aov.cpp:250-255): beta_diffuse, Li_diffuse, the diffuse part of the pending shadow ray's contribution, specular_bounce,
+        // and of the camera sample its NDC x, y and t_max - t_min
+        f3 beta_d = mk3(0.f), Li_d = mk3(0.f), nee_d = mk3(0.f), ndc = mk3(0.f);
+        auto specular_bounce = false;
         for (;;) {
             // ==== (A) lanes without a ray in flight: consume results and shade
             auto want_shadow = false, want_closest = false;
@@ -222,7 +239,10 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
             auto park_kind = kInvalid;// WF: closure kind (0 Disney, 1 Mix, 2 Layered) of the heavy surface this lane's path just reached
             if (tr.phase == kPhaseIdle && !parked) {
                 if (traced_shadow) {// direct lighting of the bounce that spawned the shadow ray, mega_path.cpp:124-130
-                    if (!tr.occluded) { Li += nee; }
+                    if (!tr.occluded) {
+                        Li += nee;
+                        if (AOV) { Li_d += nee_d; }
+                    }
                     traced_shadow = false;
                 }
                 if (traced_closest) {// one iteration of the reference's depth loop, mega_path.cpp:63-154
@@ -254,6 +274,7 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                         if (ENV && scene.env_kind != kEnvConstant) { env_evaluate(scene, tr.d, L, pdf); }
                         // (DirectLighting's camera-ray miss adds eval.L unweighted, :92-98: the same thing, pdf_bsdf = 1e16)
                         Li += beta * L * mis_bsdf(pdf * scene.env_prob);
+                        if (AOV && !specular_bounce) { Li_d += beta_d * L * mis_bsdf(pdf * scene.env_prob); }
                     }
                     SurfacePoint it;
                     auto has_surface = false;
@@ -265,12 +286,21 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
 #endif
                         it.back_facing = dot(wo, it.ng) < 0.0f;
                         if (COUNT) { local.surface_hits++; }
+                        if (AOV && depth == 0u) {// the first hit's buffers, aov.cpp:263-270 (the interaction's shading normal, not the closure's)
+                            const auto pix = static_cast<uint32_t>(pixel - film_tile);
+                            const auto dist = length(it.p - tr.o);
+                            aov_add(scene, aov_tile, LR_AOV_MASK, pix, mk3(1.f), 1u);
+                            aov_add(scene, aov_tile, LR_AOV_NORMAL, pix, it.shading.n, 3u);
+                            aov_add(scene, aov_tile, LR_AOV_DEPTH, pix, mk3(dist), 1u);
+                            aov_add(scene, aov_tile, LR_AOV_NDC, pix, mk3(ndc.x, ndc.y, dist / ndc.z), 3u);
+                        }
                         if (scene.has_lights && (it.flags & LR_SHAPE_HAS_LIGHT)) {// hit light, mega_path.cpp:79-86
                             f3 L;
                             float pdf;
                             light_evaluate(scene, it, hit.prim, tr.o, L, pdf);
                             pdf *= (1.f - scene.env_prob) / static_cast<float>(scene.light_count);
                             if (!is_direct || depth == 0u || pdf > 0.f) { Li += beta * L * mis_bsdf(pdf); }// (direct.cpp:185: light_eval.pdf > 0)
+                            if (AOV && !specular_bounce) { Li_d += beta_d * L * mis_bsdf(pdf); }
                         }
                         has_surface = (it.flags & LR_SHAPE_HAS_SURFACE) != 0u;
                         if (is_direct && depth >= 1u) { has_surface = false; }// direct.cpp:194: the loop ends after the sampled vertex
@@ -333,6 +363,17 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                             heavy.tb = tables, heavy.uv = it.uv, heavy.ng = it.ng, heavy.p = it.p, heavy.wo = wo;
                             heavy.shading = sh, heavy.closure = closure;
                         }
+                        f2 roughness{0.f, 0.f};
+                        if (AOV) {// albedo / roughness of this vertex's closure: the first hit's buffers, specular_bounce (aov.cpp:271-280, :360)
+                            f3 albedo;
+                            if (is_heavy) { heavy_albedo_roughness<MIX, LAYERED>(&heavy, &albedo, &roughness); }
+                            else { closure_albedo_roughness(closure, albedo, roughness); }
+                            if (depth == 0u) {
+                                const auto pix = static_cast<uint32_t>(pixel - film_tile);
+                                aov_add(scene, aov_tile, LR_AOV_ALBEDO, pix, albedo, 3u);
+                                aov_add(scene, aov_tile, LR_AOV_ROUGHNESS, pix, mk3(roughness.x, roughness.y, 0.f), 3u);
+                            }
+                        }
                         if (light_pdf > 0.0f) {
                             BsdfEval eval;
                             if (is_heavy) { eval = heavy_evaluate<MIX, LAYERED>(&heavy, shadow.d); }
@@ -342,6 +383,10 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                             if (is_direct && !(eval.pdf > 0.f)) { nee = mk3(0.f); }// direct.cpp:150
                             // the reference traces the shadow ray unconditionally; a zero contribution cannot change Li
                             want_shadow = nee.x != 0.f || nee.y != 0.f || nee.z != 0.f;
+                            if (AOV) {
+                                nee_d = specular_bounce ? mk3(0.f) : w * beta_d * eval.f * light_L;
+                                want_shadow = want_shadow || nee_d.x != 0.f || nee_d.y != 0.f || nee_d.z != 0.f;
+                            }
                         }
                         auto u_lobe = sampler.next_1d();
                         auto u_bsdf = direct_surfaces ? sampler.next_2d() : f2{0.f, 0.f};
@@ -360,16 +405,20 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                         ray.t_min = 0.f, ray.t_max = kFloatMax;
                         pdf_bsdf = bs.pdf;
                         beta *= (bs.pdf > 0.f ? 1.f / bs.pdf : 0.f) * bs.f;
+                        if (AOV) {
+                            if (!specular_bounce) { beta_d *= (bs.pdf > 0.f ? 1.f / bs.pdf : 0.f) * bs.f; }
+                            specular_bounce = roughness.x < .05f && roughness.y < .05f;
+                        }
                         auto eta_scale = 1.f;
                         if (has_eta) {
                             if (bs.event == kEventEnter) { eta_scale = sqr(eta); }
                             else if (bs.event == kEventExit) { eta_scale = sqr(1.f / eta); }
                         }
-                        if (any_nan(beta)) { beta = mk3(0.f); }// zero_if_any_nan
-                        auto alive = !(beta.x <= 0.f && beta.y <= 0.f && beta.z <= 0.f);
+                        if (!AOV && any_nan(beta)) { beta = mk3(0.f); }// zero_if_any_nan (the AOV integrator has neither this nor the
+                        auto alive = AOV || !(beta.x <= 0.f && beta.y <= 0.f && beta.z <= 0.f);// break on a black throughput)
                         if (is_direct && !(bs.pdf > 0.f)) { alive = false; }// direct.cpp:185: surface_sample.eval.pdf > 0
                         if (!direct_surfaces) { alive = false; }            // light-only sampling: no continuation ray
-                        auto rr = depth + 1u >= scene.rr_depth;// Russian roulette, mega_path.cpp:148-153
+                        auto rr = !AOV && depth + 1u >= scene.rr_depth;// Russian roulette, mega_path.cpp:148-153 (AOV: none)
                         auto u_rr = 0.f;
                         if (rr) { u_rr = sampler.next_1d(); }// (drawn before the closure in the reference: same stream position)
                         if (alive) {
@@ -387,6 +436,12 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                 if (WF && park_kind != kInvalid) { path_open = false; }// (it goes on elsewhere: nothing to accumulate here)
                 if (path_open && !want_shadow && !want_closest) {// path complete: film.accumulate (integrator.cpp:74)
                     if (CONT) { wf_film_accumulate(scene, args.film, pixel_index, Li * scene.shutter_weight, scene.film_clamp); }
+                    else if (AOV) {// aov.cpp:363-365: the radiance buffers instead of the film
+                        const auto pix = static_cast<uint32_t>(pixel - film_tile);
+                        aov_add(scene, aov_tile, LR_AOV_SAMPLE, pix, Li * scene.shutter_weight, 3u);
+                        aov_add(scene, aov_tile, LR_AOV_DIFFUSE, pix, Li_d * scene.shutter_weight, 3u);
+                        aov_add(scene, aov_tile, LR_AOV_SPECULAR, pix, (Li - Li_d) * scene.shutter_weight, 3u);
+                    }
                     else { film_accumulate(pixel, Li * scene.shutter_weight, scene.film_clamp); }
                     path_open = false;
                 }
@@ -455,6 +510,16 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                         camera_ray(scene, scene.filter, px, py, u_filter, u_lens, ray, weight);
                         beta = mk3(weight);
                         Li = mk3(0.f);
+                        if (AOV) {// aov.cpp:250-255, :268-269 (camera_sample.pixel: the filter's offset once more, same arithmetic)
+                            f2 off;
+                            float fw;
+                            filter_sample(scene.filter, u_filter, off, fw);
+                            const auto fx = static_cast<float>(px) + .5f + off.x, fy = static_cast<float>(py) + .5f + off.y;
+                            ndc = mk3((fx / static_cast<float>(scene.camera.width) * 2.f - 1.f) * 1.f,
+                                      (fy / static_cast<float>(scene.camera.height) * 2.f - 1.f) * -1.f, ray.t_max - ray.t_min);
+                            beta_d = beta, Li_d = mk3(0.f);
+                            specular_bounce = false;
+                        }
                         pdf_bsdf = 1e16f;
                         depth = 0u;
                         path_open = true, want_closest = true;
@@ -506,6 +571,14 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                     args.film[index] = f;
                 } else {
                     args.partial[static_cast<size_t>(chunk) * scene.camera.width * scene.camera.height + index] = acc;
+                }
+                if constexpr (AOV) {// the same for every enabled AOV channel: added in place, or this chunk's partial plane
+                    const auto pixel_count = static_cast<size_t>(scene.camera.width) * scene.camera.height;
+                    for (auto c = 0u; c < scene.aov_channels; c++) {
+                        const auto v = aov_tile[c * 64u + lane];
+                        if (args.chunk_count == 1u) { scene.aov[c * pixel_count + index] += v; }
+                        else { scene.aov_partial[(static_cast<size_t>(chunk) * scene.aov_channels + c) * pixel_count + index] = v; }
+                    }
                 }
             }
         }

@@ -31,6 +31,18 @@ template __global__ void LR_KERNEL<LR_VARIANT>(DScenePtr, RenderArgs);
 }
 
 // `device_scene`: the lrd::DScene record in device memory (lrhip_render copies it there ahead of every launch)
+#if (LR_VARIANT) & 32768// kFeatAov: the wave's LDS tiles of the AOV channels are dynamic, `lds_bytes` per block (variants.h: LR_AOV_LIST)
+extern "C" hipError_t LR_CAT(lrhip_aov_launch_, LR_VARIANT)(unsigned blocks, hipStream_t stream, const lrd::DScene *device_scene,
+                                                           const lrd::RenderArgs *args, unsigned lds_bytes) {
+    hipLaunchKernelGGL(lrd::LR_KERNEL<LR_VARIANT>, dim3(blocks), dim3(lrd::kBlockThreads), lds_bytes, stream,
+                       (lrd::DScenePtr)device_scene, *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t LR_CAT(lrhip_aov_occupancy_, LR_VARIANT)(int *blocks_per_cu, unsigned lds_bytes) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, lrd::LR_KERNEL<LR_VARIANT>, lrd::kBlockThreads, lds_bytes);
+}
+#else
 extern "C" hipError_t LR_CAT(lrhip_variant_launch_, LR_VARIANT)(unsigned blocks, hipStream_t stream, const lrd::DScene *device_scene,
                                                                const lrd::RenderArgs *args) {
     hipLaunchKernelGGL(lrd::LR_KERNEL<LR_VARIANT>, dim3(blocks), dim3(lrd::kBlockThreads), 0, stream,
@@ -41,3 +53,4 @@ extern "C" hipError_t LR_CAT(lrhip_variant_launch_, LR_VARIANT)(unsigned blocks,
 extern "C" hipError_t LR_CAT(lrhip_variant_occupancy_, LR_VARIANT)(int *blocks_per_cu) {
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, lrd::LR_KERNEL<LR_VARIANT>, lrd::kBlockThreads, 0);
 }
+#endif

@@ -40,3 +40,8 @@
 #define LR_PADDED_LIST(X) X(20482) X(20483) X(20486) X(20487) X(20490) X(20491) X(20494) X(20495) X(20498) X(20499) X(20502) X(20503) X(28690) X(28691) X(28694) X(28695) \
     /* ... and the lean passes of wavefront mode, camera pass and continuation pass, plain and with the alpha-tested traversal (the kitchen class under PaddedSobol) */ \
     X(21506) X(21507) X(21514) X(21515) X(23554) X(23555) X(23562) X(23563)
+
+// the AOV integrator (kFeatAov = 32768, src/integrators/aov.cpp): the all-closures scene mask with its counting and generic-sampler twins.
+// Not part of kSceneVariants: their launch takes the dynamic LDS of the enabled channels (megapath_variant.hip: lrhip_aov_launch_<mask>),
+// and lrhip_render asks for them by mask for AOV scenes only
+#define LR_AOV_LIST(X) X(32892) X(32893) X(32894) X(32895)

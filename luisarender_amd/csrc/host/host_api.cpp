@@ -109,10 +109,22 @@ const char *lrhost_scene_camera_file(const lrhost_scene *scene, int camera_index
 
 int lrhost_scene_has_lighting(const lrhost_scene *scene) { return scene->data->has_lighting() ? 1 : 0; }
 
+int lrhost_scene_aov_settings(const lrhost_scene *scene, uint32_t *noisy_count, uint32_t *dump) {
+    return guarded([&] {
+        if (scene->data->integrator.kind != LR_INTEGRATOR_AOV) { throw lr::Error{"The scene's integrator is not AOV."}; }
+        if (noisy_count) { *noisy_count = scene->data->aov_noisy_count; }
+        if (dump) { *dump = scene->data->aov_dump; }
+    });
+}
+
 void lrhost_scene_destroy(lrhost_scene *scene) { delete scene; }
 
 int lrhost_save_image(const char *path, const float *rgba, uint32_t width, uint32_t height) {
     return guarded([&] { lr::save_image(path, rgba, width, height); });
+}
+
+int lrhost_save_image_channels(const char *path, const float *pixels, uint32_t width, uint32_t height, uint32_t channels) {
+    return guarded([&] { lr::save_image(path, pixels, width, height, channels); });
 }
 
 int lrhost_load_image(const char *path, float **rgba, uint32_t *width, uint32_t *height, uint32_t *channels) {

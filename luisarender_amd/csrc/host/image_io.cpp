@@ -27,14 +27,22 @@ template<typename T>
 void put(std::string &buf, T v) { buf.append(reinterpret_cast<const char *>(&v), sizeof(T)); }
 void put_str(std::string &buf, const char *s) { buf.append(s, std::strlen(s) + 1u); }
 
-void write_exr(const fs::path &path, const float *rgba, uint32_t w, uint32_t h) {
+// `nc` interleaved channels per pixel: 4 = RGBA, 3 = RGB, 1 = one value.  The channel list is alphabetical and the scanlines follow it:
+// A B G R, B G R, or a lone A -- what tinyexr's SaveEXR writes for 4, 3 and 1 components (from memory of tinyexr, which is not part of
+// the reference snapshot: it names a single component "A"), all FLOAT here
+void write_exr(const fs::path &path, const float *rgba, uint32_t w, uint32_t h, uint32_t nc = 4u) {
+    static constexpr const char *kNames4[4] = {"A", "B", "G", "R"}, *kNames3[3] = {"B", "G", "R"}, *kNames1[1] = {"A"};
+    static constexpr int kOrder4[4] = {3, 2, 1, 0}, kOrder3[3] = {2, 1, 0}, kOrder1[1] = {0};// source channel of each stored one
+    const auto names = nc == 4u ? kNames4 : nc == 3u ? kNames3 : kNames1;
+    const auto order = nc == 4u ? kOrder4 : nc == 3u ? kOrder3 : kOrder1;
     std::string head;
     put<uint32_t>(head, 20000630u);// magic
     put<uint32_t>(head, 2u);       // version 2, scanline, single part
-    // channels (alphabetical): A B G R, all FLOAT (pixel type 2)
+    // channels (alphabetical), all FLOAT (pixel type 2)
     put_str(head, "channels"), put_str(head, "chlist");
-    put<uint32_t>(head, 4u * 18u + 1u);
-    for (auto name : {"A", "B", "G", "R"}) {
+    put<uint32_t>(head, nc * 18u + 1u);
+    for (uint32_t k = 0u; k < nc; k++) {
+        const auto name = names[k];
         put_str(head, name);
         put<uint32_t>(head, 2u);// FLOAT
         put<uint8_t>(head, 0u); // pLinear
@@ -55,7 +63,7 @@ void write_exr(const fs::path &path, const float *rgba, uint32_t w, uint32_t h) 
     put_str(head, "screenWindowWidth"), put_str(head, "float"), put<uint32_t>(head, 4u), put<float>(head, 1.f);
     put<uint8_t>(head, 0u);// end of header
 
-    auto line_bytes = static_cast<uint64_t>(w) * 16u;
+    auto line_bytes = static_cast<uint64_t>(w) * 4u * nc;
     auto table_offset = head.size();
     auto data_offset = table_offset + static_cast<uint64_t>(h) * 8u;
     std::ofstream f{path, std::ios::binary};
@@ -65,16 +73,15 @@ void write_exr(const fs::path &path, const float *rgba, uint32_t w, uint32_t h) 
         auto off = data_offset + static_cast<uint64_t>(y) * (8u + line_bytes);
         f.write(reinterpret_cast<const char *>(&off), 8);
     }
-    std::vector<float> line(static_cast<size_t>(w) * 4u);
+    std::vector<float> line(static_cast<size_t>(w) * nc);
     for (uint32_t y = 0; y < h; y++) {
         auto yy = static_cast<int32_t>(y);
         auto size = static_cast<uint32_t>(line_bytes);
         f.write(reinterpret_cast<const char *>(&yy), 4);
         f.write(reinterpret_cast<const char *>(&size), 4);
-        static constexpr int order[4] = {3, 2, 1, 0};// A B G R
-        for (auto c = 0; c < 4; c++) {
+        for (uint32_t c = 0u; c < nc; c++) {
             for (uint32_t x = 0; x < w; x++) {
-                line[static_cast<size_t>(c) * w + x] = rgba[(static_cast<size_t>(y) * w + x) * 4u + static_cast<size_t>(order[c])];
+                line[static_cast<size_t>(c) * w + x] = rgba[(static_cast<size_t>(y) * w + x) * nc + static_cast<size_t>(order[c])];
             }
         }
         f.write(reinterpret_cast<const char *>(line.data()), static_cast<std::streamsize>(line_bytes));
@@ -95,13 +102,18 @@ void float_to_rgbe(const float *rgb, uint8_t *out) {
     out[3] = static_cast<uint8_t>(e + 128);
 }
 
-void write_hdr(const fs::path &path, const float *rgba, uint32_t w, uint32_t h) {
+// (nc = 1: the value as gray)
+void write_hdr(const fs::path &path, const float *rgba, uint32_t w, uint32_t h, uint32_t nc = 4u) {
     std::ofstream f{path, std::ios::binary};
     if (!f) { throw Error{"Failed to save film to '" + path.string() + "'."}; }
     f << "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y " << h << " +X " << w << "\n";
     std::vector<uint8_t> line(static_cast<size_t>(w) * 4u);
     for (uint32_t y = 0; y < h; y++) {
-        for (uint32_t x = 0; x < w; x++) { float_to_rgbe(rgba + (static_cast<size_t>(y) * w + x) * 4u, &line[x * 4u]); }
+        for (uint32_t x = 0; x < w; x++) {
+            const auto px = rgba + (static_cast<size_t>(y) * w + x) * nc;
+            const float gray[3] = {px[0], px[0], px[0]};
+            float_to_rgbe(nc == 1u ? gray : px, &line[x * 4u]);
+        }
         f.write(reinterpret_cast<const char *>(line.data()), static_cast<std::streamsize>(line.size()));
     }
 }
@@ -822,7 +834,8 @@ LoadedImage read_pnm(const fs::path &path) {
 
 }// namespace
 
-void save_image(const std::string &path_in, const float *rgba, uint32_t width, uint32_t height) {
+void save_image(const std::string &path_in, const float *rgba, uint32_t width, uint32_t height, uint32_t channels) {
+    if (channels != 1u && channels != 3u && channels != 4u) { throw Error{"save_image: 1, 3 or 4 channels per pixel."}; }
     fs::path path{path_in};
     auto ext = lower_ext(path);
     if (ext != ".exr" && ext != ".hdr") {
@@ -831,7 +844,7 @@ void save_image(const std::string &path_in, const float *rgba, uint32_t width, u
         ext = ".exr";
     }
     if (auto folder = path.parent_path(); !folder.empty() && !fs::exists(folder)) { fs::create_directories(folder); }
-    if (ext == ".exr") { write_exr(path, rgba, width, height); } else { write_hdr(path, rgba, width, height); }
+    if (ext == ".exr") { write_exr(path, rgba, width, height, channels); } else { write_hdr(path, rgba, width, height, channels); }
 }
 
 LoadedImage load_image(const std::string &path_in) {

@@ -10,7 +10,8 @@
 // Compiled three times: LR_PLUGIN_IMPL = "megapath" (default), "direct" (DirectLighting, src/integrators/direct.cpp) and
 // "normal" (NormalVisualizer, src/integrators/normal.cpp) — the sibling integrators of SURVEY §8 f4 are run-time modes of
 // the same megakernel (lr_integrator.kind, set by the scene loader from the node's impl type), so their plugins differ
-// only in the name they register and in NormalVisualizer not needing a light.
+// only in the name they register and in NormalVisualizer not needing a light.  "aov" (AuxiliaryBufferPathTracing,
+// src/integrators/aov.cpp) has a render loop of its own (render_aov below): no film, the auxiliary buffers dumped as it goes.
 #include <dlfcn.h>
 
 #include <chrono>
@@ -44,6 +45,7 @@ struct HipApi {
     decltype(&lrhip_synchronize) synchronize{};
     decltype(&lrhip_film_download) film_download{};
     decltype(&lrhip_last_error) last_error{};
+    decltype(&lrhip_aov_download) aov_download{};// the AOV integrator
     // multi-GPU: only looked up when the frame is sharded
     decltype(&lrhip_comm_init_all) comm_init_all{};
     decltype(&lrhip_comm_destroy) comm_destroy{};
@@ -65,6 +67,7 @@ struct HipApi {
         LR_SYM(synchronize, "lrhip_synchronize");
         LR_SYM(film_download, "lrhip_film_download");
         LR_SYM(last_error, "lrhip_last_error");
+        LR_SYM(aov_download, "lrhip_aov_download");
         LR_SYM(comm_init_all, "lrhip_comm_init_all");
         LR_SYM(comm_destroy, "lrhip_comm_destroy");
         LR_SYM(film_reduce_group, "lrhip_film_reduce_group");
@@ -72,6 +75,80 @@ struct HipApi {
         return create && destroy && upload_scene && update_scene && film_clear && render && synchronize && film_download && last_error;
     }
 };
+
+// AuxiliaryBufferPathTracingInstance::_render_one_camera (aov.cpp:202-439), camera by camera on ONE GPU: noisy_count samples per pixel,
+// one launch per sample (aov.cpp:410-412: one dispatch each), the auxiliary buffers cleared at the start of every shutter sample and
+// written as <parent>/<stem>_<component>_<n:05><ext> (<stem>_<component><ext> for the final dump) at the counts the dump strategy names,
+// each divided by float(1.0 / n) on the host (AuxiliaryBuffer::save, aov.cpp:173-189).  The camera's own file is never written.
+template<typename Api, typename Data>
+void render_aov(Api &api, int device, Data &data, bool has_lighting) {
+    lrhip_ctx *ctx = nullptr;
+    auto die = [&](const char *what) {
+        std::fprintf(stderr, "[error] %s: %s\n", what, api.last_error());
+        std::abort();
+    };
+    if (api.aov_download == nullptr) {
+        std::fprintf(stderr, "[error] liblrhip.so has no lrhip_aov_download\n");
+        std::abort();
+    }
+    if (api.create(device, &ctx) != LRHIP_OK) { die("lrhip_create"); }
+    static const char *const kNames[LR_AOV_COMPONENTS] = {"sample", "diffuse", "specular", "normal", "albedo", "depth", "roughness", "ndc", "mask"};
+    for (size_t i = 0; i < data.cameras.size(); i++) {
+        auto &camera = data.cameras[i];
+        if (!has_lighting) {// aov.cpp:209-213: nothing is written
+            lr::log_warning("No lights in scene. Rendering aborted.");
+            continue;
+        }
+        const auto aux_spp = data.aov_noisy_count;
+        auto shutter = camera.shutter_samples;
+        if (shutter.size() != 1u && camera.camera.spp != aux_spp) {// aov.cpp:393-395
+            std::fprintf(stderr, "[error] AOVIntegrator is not compatible with motion blur if rendered with different spp from the camera.\n");
+            std::abort();
+        }
+        if (aux_spp != camera.camera.spp) { shutter = {lr::ShutterSample{camera.shutter_span[0], 1.f, aux_spp}}; }// aov.cpp:396-402
+        const auto width = camera.camera.width, height = camera.camera.height;
+        const auto tiles = ((width + 7u) / 8u) * ((height + 7u) / 8u);
+        const std::filesystem::path file{camera.file};
+        const auto parent = file.parent_path();
+        const auto stem = file.stem().string(), ext = file.extension().string();
+        std::fprintf(stderr, "[info] Rendering the AOVs of '%s' of resolution %ux%u at %uspp.\n", camera.file.c_str(), width, height, aux_spp);
+        const auto t0 = std::chrono::steady_clock::now();
+        auto sample_count = 0u;
+        auto first = true;
+        std::vector<float> buffer;
+        for (auto &s : shutter) {
+            const auto moved = lr::set_scene_time(data, s.time);
+            auto view = data.view(i);
+            if ((first || moved) && (first ? api.upload_scene(ctx, &view) : api.update_scene(ctx, &view)) != LRHIP_OK) { die("lrhip_upload_scene"); }
+            first = false;
+            if (api.film_clear(ctx) != LRHIP_OK) { die("lrhip_film_clear"); }// clear_auxiliary_buffers at EVERY shutter sample (aov.cpp:406)
+            for (auto k = 0u; k < s.spp; k++) {
+                lrhip_render_params params{sample_count, sample_count + 1u, 0u, tiles, 1u, LRHIP_RENDER_SHUTTER_WEIGHT, 1u, s.weight};
+                if (api.render(ctx, &params) != LRHIP_OK || api.synchronize(ctx) != LRHIP_OK) { die("lrhip_render"); }
+                sample_count++;
+                // should_dump, aov.cpp:383-392
+                const auto n = sample_count;
+                const auto dump = data.aov_dump == LR_AOV_DUMP_ALL || (data.aov_dump == LR_AOV_DUMP_FINAL ? n == aux_spp : (n & (n - 1u)) == 0u);
+                if (!dump) { continue; }
+                const auto scale = static_cast<float>(1. / n);
+                for (uint32_t c = 0u; c < LR_AOV_COMPONENTS; c++) {
+                    if ((data.integrator.flags & LR_AOV_BIT(c)) == 0u) { continue; }
+                    const auto channels = (c == LR_AOV_DEPTH || c == LR_AOV_MASK) ? 1u : 3u;
+                    buffer.assign(static_cast<size_t>(width) * height * channels, 0.f);
+                    if (api.aov_download(ctx, c, buffer.data()) != LRHIP_OK) { die("lrhip_aov_download"); }
+                    for (auto &v : buffer) { v *= scale; }
+                    char count[16];
+                    std::snprintf(count, sizeof(count), "_%05u", n);
+                    const auto name = stem + "_" + kNames[c] + (data.aov_dump == LR_AOV_DUMP_FINAL ? std::string{} : std::string{count}) + ext;
+                    lr::save_image((parent / name).string(), buffer.data(), width, height, channels);
+                }
+            }
+        }
+        const auto ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        std::fprintf(stderr, "[info] Rendering finished in %g ms.\n", ms);
+    }
+    api.destroy(ctx);
+}
 
 }// namespace
 
@@ -103,6 +180,13 @@ public:
         if (!api.load(scene.runtime_directory())) {
             std::fprintf(stderr, "[error] Failed to load liblrhip.so (the gfx950 megakernel library): %s\n", dlerror());
             std::abort();// LUISA_ERROR semantics: log + abort
+        }
+        if (data.integrator.kind == LR_INTEGRATOR_AOV) {
+            auto device = 0;
+            if (stream.device != nullptr) { device = std::max(stream.device->indices.size() > 1u ? stream.device->indices.front() : stream.device->index, 0); }
+            if (stream.device != nullptr && stream.device->indices.size() > 1u) { lr::log_warning("The AOV integrator renders on the first listed device only."); }
+            render_aov(api, device, data, pipeline().has_lighting());
+            return;
         }
         // One lrhip_ctx per GPU.  `-d 0,1,2,3` / LR_DEVICES shards every frame by screen tile over the listed devices:
         // this process flattens the scene and builds the BVH ONCE, one host thread per GPU uploads the same host tables and renders

@@ -4,6 +4,7 @@
 #include <dlfcn.h>
 
 #include <array>
+#include <cctype>
 #include <cstring>
 #include <filesystem>
 #include <fstream>
@@ -108,6 +109,7 @@ lr_scene SceneData::view(size_t camera_index) const {
     s.film = cameras[camera_index].film;
     s.sampler = sampler;
     s.sampler.spp = s.camera.spp;// sampler()->reset(.., resolution, pixel_count, spp), integrator.cpp:59
+    if (integrator.kind == LR_INTEGRATOR_AOV) { s.sampler.spp = aov_noisy_count; }// (aov.cpp:205-216: noisy_count in place of the camera's)
     s.sampler.scale = next_pow2(std::max(s.camera.width, s.camera.height));
     if (sampler.tile_size[0] != 0u) {// TileSharedSamplerInstance::reset (tile_shared.cpp:44-50): the base sees the tile grid as its resolution
         const auto tw = std::min(s.camera.width, sampler.tile_size[0]), th = std::min(s.camera.height, sampler.tile_size[1]);
@@ -1326,6 +1328,35 @@ public:
             _out.integrator.max_depth = std::max(integrator->uint_or("depth", 20u), 1u);
             _out.integrator.rr_depth = integrator->uint_or("rr_depth", 0u);
             _out.integrator.rr_threshold = std::max(integrator->float_or("rr_threshold", 0.95f), 0.05f);
+        } else if (integrator->impl_type() == "aov") {// AuxiliaryBufferPathTracing, aov.cpp:48-87
+            _out.integrator.kind = LR_INTEGRATOR_AOV;
+            _out.integrator.max_depth = std::max(integrator->uint_or("depth", 10u), 1u);
+            // parsed as the reference does, never used: the AOV estimator has no Russian roulette (aov.cpp:257-362)
+            _out.integrator.rr_depth = integrator->uint_or("rr_depth", 0u);
+            _out.integrator.rr_threshold = std::max(integrator->float_or("rr_threshold", 0.95f), 0.05f);
+            _out.aov_noisy_count = std::max(integrator->uint_or("noisy_count", 8u), 8u);
+            static const char *const kNames[LR_AOV_COMPONENTS] = {"sample", "diffuse", "specular", "normal", "albedo", "depth", "roughness", "ndc", "mask"};
+            auto lower = [](std::string v) {
+                for (auto &c : v) { c = static_cast<char>(std::tolower(static_cast<unsigned char>(c))); }
+                return v;
+            };
+            auto flags = 0u;
+            for (auto &name : integrator->strings_opt("components").value_or(std::vector<std::string>{"all"})) {
+                auto comp = lower(name);
+                if (comp == "all") { flags |= LR_AOV_ALL; continue; }
+                auto k = 0u;
+                while (k < LR_AOV_COMPONENTS && comp != kNames[k]) { k++; }
+                if (k < LR_AOV_COMPONENTS) { flags |= LR_AOV_BIT(k); }
+                else { log_warning("Ignoring unknown AOV component '" + comp + "'. [" + integrator->location() + "]"); }
+            }
+            _out.integrator.flags = flags;
+            auto dump = lower(integrator->string_or("dump", "power2"));
+            if (dump == "all") { _out.aov_dump = LR_AOV_DUMP_ALL; }
+            else if (dump == "final") { _out.aov_dump = LR_AOV_DUMP_FINAL; }
+            else {
+                if (dump != "power2") { log_warning("Unknown dump strategy '" + dump + "'. Fallback to power2 strategy. [" + integrator->location() + "]"); }
+                _out.aov_dump = LR_AOV_DUMP_POWER2;
+            }
         } else {
             throw Error{"Integrator '" + integrator->impl_type() + "' is out of scope: this framework implements the MegaPath hot "
                         "path and its sibling megakernels Direct / Normal / MegaVPTNaive (SURVEY §2 row 21, §8 f3-f4)."};

@@ -77,6 +77,8 @@ struct SceneData {
     std::vector<uint64_t> vdc_sobol, vdc_sobol_inv;// all rows [25|26][52]; view() points at the row of the camera's scale
     lr_integrator integrator{};
     std::string integrator_impl;
+    uint32_t aov_noisy_count{8u};          // the AOV integrator (aov.cpp:53): samples per pixel, in place of the camera's
+    uint32_t aov_dump{LR_AOV_DUMP_POWER2}; // LR_AOV_DUMP_*
     bool any_non_opaque{false};
     // animation (src/transforms/lerp.cpp, Geometry::update geometry.cpp:194-216, Pipeline::update pipeline.cpp:101-113)
     std::vector<XformNode> xforms;
@@ -140,7 +142,8 @@ LoadedMesh loop_subdivide(const std::vector<lr_vertex> &vertices, const std::vec
 LoadedMesh make_sphere_mesh(uint32_t subdivision);
 
 // image_io.cpp
-void save_image(const std::string &path, const float *rgba, uint32_t width, uint32_t height);// src/util/imageio.cpp:694-726
+// src/util/imageio.cpp:694-726; channels: 4 (RGBA), 3 (RGB) or 1 interleaved floats per pixel (the AOV integrator's buffers)
+void save_image(const std::string &path, const float *rgba, uint32_t width, uint32_t height, uint32_t channels = 4u);
 struct LoadedImage {
     uint32_t width{0}, height{0}, channels{0};
     bool is_hdr{false};

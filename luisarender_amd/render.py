@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from . import _ffi
-from .scene import Scene
+from .scene import AOV_COMPONENTS, Scene, aov_channels
 
 
 class DeviceError(RuntimeError):
@@ -17,6 +17,23 @@ class DeviceError(RuntimeError):
 
 def tile_count(width: int, height: int) -> int:
     return ((width + 7) // 8) * ((height + 7) // 8)
+
+
+def aov_dump_counts(noisy_count: int, dump: str) -> list[int]:
+    """The AOV integrator's should_dump (aov.cpp:383-392): the sample counts after which its buffers are written -- powers of two
+    (so none at noisy_count 10 itself), every count, or noisy_count alone"""
+    if dump == "all":
+        return list(range(1, noisy_count + 1))
+    if dump == "final":
+        return [noisy_count]
+    return [n for n in range(1, noisy_count + 1) if n & (n - 1) == 0]
+
+
+def aov_file_name(camera_file: str, component: str, n: int, dump: str) -> str:
+    """aov.cpp:418-421: <parent>/<stem>_<component>_<n:05><ext>, or <parent>/<stem>_<component><ext> for the final dump"""
+    parent, name = os.path.split(camera_file)
+    stem, ext = os.path.splitext(name)
+    return os.path.join(parent, f"{stem}_{component}{'' if dump == 'final' else f'_{n:05d}'}{ext}")
 
 
 class MegaPathRenderer:
@@ -29,6 +46,7 @@ class MegaPathRenderer:
         self._check(self._lib.lrhip_create(device, C.byref(self._ctx)))
         self._scene = None
         self.width = self.height = 0
+        self._aov_samples = 0  # samples per pixel rendered since the last upload / clear (download_aov's normalisation)
 
     def _check(self, rc: int) -> None:
         if rc != 0:
@@ -43,12 +61,16 @@ class MegaPathRenderer:
         self._check((self._lib.lrhip_update_scene if keep_film else self._lib.lrhip_upload_scene)(self._ctx, C.byref(view)))
         self._scene = scene
         self.width, self.height = int(view.camera.width), int(view.camera.height)
+        if not keep_film:
+            self._aov_samples = 0
 
     def bind_film(self, device_ptr: int | None) -> None:
         self._check(self._lib.lrhip_bind_film(self._ctx, C.c_void_p(device_ptr or 0)))
 
     def clear(self) -> None:
+        """lrhip_film_clear: the film and, for the AOV integrator, its buffers"""
         self._check(self._lib.lrhip_film_clear(self._ctx))
+        self._aov_samples = 0
 
     def render(self, spp_begin: int, spp_end: int, rank: int = 0, world: int = 1, counters: bool = False,
                sync: bool = False, balance_shards: int = 1, shutter_weight: float | None = None, tile_end: int | None = None) -> None:
@@ -66,6 +88,7 @@ class MegaPathRenderer:
             p.flags |= 2
             p.shutter_weight = shutter_weight
         self._check(self._lib.lrhip_render(self._ctx, C.byref(p)))
+        self._aov_samples += spp_end - spp_begin
         if sync:
             self.synchronize()
 
@@ -90,6 +113,16 @@ class MegaPathRenderer:
     def download(self, converted: bool = True) -> np.ndarray:
         out = np.empty((self.height, self.width, 4), np.float32)
         self._check(self._lib.lrhip_film_download(self._ctx, out.ctypes.data, 1 if converted else 0))
+        return out
+
+    def download_aov(self, name: str, normalized: bool = True) -> np.ndarray:
+        """lrhip_aov_download: the AOV integrator's buffer `name` (AOV_COMPONENTS) as [H, W, channels], row 0 at the top.
+        normalized: times float(1 / n) for the n samples per pixel rendered since the last upload or clear(), as the reference
+        writes its files (AuxiliaryBuffer::save, aov.cpp:184-185); otherwise the raw sums"""
+        out = np.empty((self.height, self.width, aov_channels(name)), np.float32)
+        self._check(self._lib.lrhip_aov_download(self._ctx, AOV_COMPONENTS.index(name), out.ctypes.data))
+        if normalized:
+            out *= np.float32(1.0 / max(self._aov_samples, 1))
         return out
 
     # ---- the one collective of the multi-GPU path (SURVEY 8e), through the C ABI

@@ -12,6 +12,16 @@ class HostError(RuntimeError):
     pass
 
 
+# the AOV integrator's components in lr_scene.h LR_AOV_* order (bit k of lr_integrator.flags) and its dump strategies (LR_AOV_DUMP_*)
+AOV_COMPONENTS = ("sample", "diffuse", "specular", "normal", "albedo", "depth", "roughness", "ndc", "mask")
+AOV_DUMPS = ("power2", "all", "final")
+
+
+def aov_channels(component: str) -> int:
+    """floats per pixel of an AOV buffer: depth and mask 1, every other component 3 (roughness is (rx, ry, 0), aov.cpp:157)"""
+    return 1 if component in ("depth", "mask") else 3
+
+
 class Scene:
     """A parsed + flattened scene (lrhost_scene) and its POD view (lr_scene)."""
 
@@ -98,6 +108,16 @@ class Scene:
     def has_lighting(self) -> bool:
         return bool(self._lib.lrhost_scene_has_lighting(self._handle))
 
+    def aov_settings(self) -> dict:
+        """The AOV integrator's settings (src/integrators/aov.cpp:48-87): the enabled components (AOV_COMPONENTS order), noisy_count (samples
+        per pixel, in place of the camera's spp), the dump strategy and the path depth.  HostError for any other integrator."""
+        n, dump = C.c_uint32(), C.c_uint32()
+        if self._lib.lrhost_scene_aov_settings(self._handle, C.byref(n), C.byref(dump)) != 0:
+            raise HostError(self._lib.lrhost_last_error().decode())
+        integrator = self.view().integrator
+        return {"components": [c for k, c in enumerate(AOV_COMPONENTS) if (integrator.flags >> k) & 1], "noisy_count": n.value,
+                "dump": AOV_DUMPS[dump.value], "depth": int(integrator.max_depth)}
+
     def resolution(self, camera: int = 0) -> tuple[int, int]:
         v = self.view(camera)
         return int(v.camera.width), int(v.camera.height)
@@ -116,11 +136,17 @@ class Scene:
 
 
 def save_image(path: str, rgba: np.ndarray) -> None:
-    """save_image of the reference (src/util/imageio.cpp:694-726): float RGBA -> .exr / .hdr"""
+    """save_image of the reference (src/util/imageio.cpp:694-726): float RGBA -> .exr / .hdr.  [H, W, 3] is written as RGB and
+    [H, W] / [H, W, 1] as one channel (the AOV integrator's buffers: EXR channel "A", HDR gray)"""
     lib = _ffi.host_lib()
     rgba = np.ascontiguousarray(rgba, dtype=np.float32)
     h, w = rgba.shape[:2]
-    if lib.lrhost_save_image(path.encode(), rgba.ctypes.data, w, h) != 0:
+    channels = 1 if rgba.ndim == 2 else rgba.shape[2]
+    if channels == 4:
+        rc = lib.lrhost_save_image(path.encode(), rgba.ctypes.data, w, h)
+    else:
+        rc = lib.lrhost_save_image_channels(path.encode(), rgba.ctypes.data, w, h, channels)
+    if rc != 0:
         raise HostError(lib.lrhost_last_error().decode())
 
 
