@@ -30,8 +30,8 @@ HOST_HDR := $(wildcard $(HOSTDIR)/*.h) $(wildcard include/*.h)
 HIP_SRC := $(HIPDIR)/lrhip.hip
 HIP_HDR := $(wildcard $(HIPDIR)/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow
-all: host oracle hip cli ieee shallow
+.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly
+all: host oracle hip cli ieee shallow noearly
 
 # oracle/_ref: the reference's OWN sources compiled in place against the scalar LuisaCompute stand-in of oracle/ref_shim
 # (test infrastructure: pins oracle/ to the reference; needs /root/reference, so only where the reference tree exists)
@@ -130,6 +130,13 @@ $(LIBDIR)/variants/liblrhip_ieee.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $
 shallow: $(LIBDIR)/variants/liblrhip_shallow.so
 $(LIBDIR)/variants/liblrhip_shallow.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
 	$(MAKE) --no-print-directory hip-variant NAME=shallow DEFS='-DLR_STACK_LDS=4' VARIANT_MASKS='0 1 4096 4097' HEAVY_MASKS=
+
+# The lean pool kernels once more with the round 5-6 order of an iteration: its fetch requests BEHIND the tail of the iteration before
+# (megapool_kernel.h: LR_POOL_EARLY_FETCH).  TEST INFRASTRUCTURE: the shipped order moves memory requests and nothing else, so its frames
+# and its ray / node / triangle counters must equal this library's (tests/test_gpu_early_fetch.py).
+noearly: $(LIBDIR)/variants/liblrhip_noearly.so
+$(LIBDIR)/variants/liblrhip_noearly.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
+	$(MAKE) --no-print-directory hip-variant NAME=noearly DEFS='-DLR_POOL_EARLY_FETCH=0' VARIANT_MASKS='4096 4097 4100 4101' HEAVY_MASKS=
 
 cli: $(BINDIR)/luisa-render-cli
 $(BINDIR)/luisa-render-cli: $(HOSTDIR)/cli.cpp $(HOSTDIR)/plugin_megapath.cpp $(LIBDIR)/liblrhost.so $(HOST_HDR)

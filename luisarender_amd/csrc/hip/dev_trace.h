@@ -65,6 +65,7 @@ struct TraceStats {
     uint32_t steps, steps_busy;// loop iterations of the wave / iterations in which this lane did work
     uint32_t steps_starved;    // iterations this lane sat out because its pixel had no samples left to start
     uint32_t nodes_empty;      // node visits without a hit child
+    uint32_t early_fetch_broken;// pool kernels, LR_POOL_EARLY_FETCH: iterations in which this lane consumed something other than what was requested for it (must be 0)
 #ifdef LR_STALL_PROBE
     uint32_t probe_lds;// LDS byte address of this wave's probe words (eight section sums + the last timestamp), 0 = not a sampled wave: THE STALL PROBE below
 #endif
@@ -90,6 +91,7 @@ struct TraceStats {
 //   tail      end of the iteration: votes, turnover of ended rays, exit tests
 //   leaf_wait serial flow only (ALPHA pool kernels, one-path kernels): the leaf step's own wait for its triangle
 enum : uint32_t { kProbeIssue, kProbeVmWait, kProbeLeaf, kProbePacket, kProbeSlab, kProbeChain, kProbeTail, kProbeLeafWait, kProbeSlots };
+constexpr uint32_t kProbeEarlyFetchBroken = 15u;// lrhip_counters::probe word of the counting pool kernels' early-fetch check, builds WITHOUT the stall probe (megapool_kernel.h: pool_trace)
 #ifdef LR_STALL_PROBE
 LR_D uint32_t probe_now() {
     unsigned long long t;
@@ -498,6 +500,21 @@ LR_D LeafTriangle trav_leaf_fetch(const TravLane &tl, uint32_t ref) {
     // (non-temporal loads here -- a leaf's triangle is touched once -- were measured in round 4: C2 854 -> 761 Msamples/s)
     return LeafTriangle{tb[0], tb[1], tb[2]};
 }
+// the triangle requests of an iteration of the fused flow (trav_requests below): every lane at a leaf asks for its triangle
+struct LeafRequest {
+    LeafTriangle tri;
+    bool at_leaf;// the lane stands at a leaf and its triangle is on its way
+};
+LR_D void trav_leaf_requests(const TravLane &tl, const TravState &tr, LeafRequest &rq) {
+    // (the lanes that fetch no triangle never read one: their registers need a DEFINED value, not a particular one -- an empty asm "writes" them
+    // instead of the ten v_mov_b32 per iteration of `LeafTriangle tri{}`: 259 -> 250 VALU instructions in the pool loop, C2 1091 -> 1101, C3 1087 ->
+    // 1100, C4 1224 -> 1235 Msamples/s, films bit-identical now that trav_leaf_test's arithmetic is written out: profiles/r06zn_triangle_test_written_out.txt)
+    auto &tri = rq.tri;
+    asm volatile("" : "=v"(tri.a.x), "=v"(tri.a.y), "=v"(tri.a.z), "=v"(tri.a.w), "=v"(tri.b.x), "=v"(tri.b.y), "=v"(tri.b.z), "=v"(tri.b.w),
+                      "=v"(tri.c.x), "=v"(tri.c.y), "=v"(tri.c.z), "=v"(tri.c.w));
+    rq.at_leaf = static_cast<int>(tr.cur) < static_cast<int>(kCurParked);
+    if (rq.at_leaf) { tri = trav_leaf_fetch(tl, tr.cur); }
+}
 // the triangle test of a lane at leaf `ref`; returns true if the ray has found an occluder (a shadow ray's hit: the rest of its stack is dropped)
 template<bool COUNT, bool ALPHA>
 LR_D bool trav_leaf_test(TravState &tr, uint32_t ref, const LeafTriangle &tri, TraceStats &stats) {
@@ -617,6 +634,46 @@ LR_D void trav_leaf_step(const TraversalStack &stack, const TravLane &tl, TravSt
 // 3662 against 4029.  It executes more instructions (five exec regions per iteration instead of two, unconditional address arithmetic),
 // and a wave issues at most one instruction of ANY kind every ~4.5 cycles: what an iteration costs a wave is its instruction count --
 // scalar and branch instructions included -- as much as the round trips it waits for.
+//
+// THE FUSED FLOW IN TWO HALVES (LR_POOL_FUSED_FETCH, megapool_kernel.h): trav_requests sends out both gathers of an iteration -- the packets of the
+// lanes at inner nodes into the staging area, the triangles of the lanes at leaves into registers (LeafRequest) -- and trav_consume waits for them
+// once, tests the triangles, pops, and runs the node step; a lane the node step sends to a leaf tests it in the NEXT iteration.  What a lane asks
+// for is a function of its `cur` alone, so a caller may put code between the two halves that leaves alone the `cur` of every lane at a node or a
+// leaf (pool_trace: LR_POOL_EARLY_FETCH).
+// ALWAYS: the four packet loads go out even when no lane of the wave stands at an inner node (every lane then asks for packet 0, as the lanes
+// without a node always do): what pool_trace needs when rays may START between the two halves -- they start at the root, packet 0.
+template<bool COUNT, bool ALWAYS>
+LR_D bool trav_requests(const TraversalStack &stack, const TravLane &tl, const TravState &tr, LeafRequest &rq, bool leaves, TraceStats &stats) {
+    const auto is_inner = static_cast<int>(tr.cur) >= 0;
+    const auto any_inner = ALWAYS || lr_any(is_inner);
+    prio_chain();
+    if (any_inner) { trav_node_fetch(stack, tl, tr, is_inner); }
+    if (leaves) { trav_leaf_requests(tl, tr, rq); }
+    LR_MARK(kProbeIssue);
+    (void)stats;
+    return any_inner;// the packet loads went out
+}
+// `any_inner`: some lane stands at an inner node NOW (its packet is among the requested ones); `deep`: some lane may reach the HBM overflow area of
+// the stack in this iteration (trav_iteration)
+template<bool COUNT, bool ALPHA>
+LR_D void trav_consume(const TraversalStack &stack, const TravLane &tl, TravState &tr, uint32_t &spb, f3 inv, LeafRequest &rq, bool any_inner, bool deep, TraceStats &stats) {
+    const auto is_inner = static_cast<int>(tr.cur) >= 0;
+    auto &tri = rq.tri;
+    prio_tests();
+    trav_fetch_wait();
+    LR_MARK(kProbeVmWait);
+    LR_PIN2(tri.a.x, tri.b.x, tri.c.x, tri.c.w);
+    if (rq.at_leaf) {
+        if (trav_leaf_test<COUNT, ALPHA>(tr, tr.cur, tri, stats)) { spb = tl.lds_base; }
+        if (!ALPHA || !(tr.phase & kPhasePendingAlpha)) { tr.cur = trav_pop(stack, tl, spb, deep); }
+        else { tr.cur |= kCurParkBit; }
+    }
+    LR_MARK2(kProbeLeaf, tr.cur, spb);
+    if (any_inner) { trav_node_step<COUNT, true>(stack, tl, tr, spb, inv, is_inner, deep, stats); }
+#if defined(LR_STALL_PROBE) && LR_STALL_PROBE < 2
+    LR_MARK(kProbeChain, tr.cur, spb);// (level 1: everything of the walk behind the wait -- triangle test, slab tests, sort, pushes / pops)
+#endif
+}
 template<bool COUNT, bool ALPHA, bool FUSED = false>
 LR_D void trav_iteration(const TraversalStack &stack, const TravLane &tl, TravState &tr, uint32_t &spb, f3 inv, TraceStats &stats) {
     const auto is_inner = static_cast<int>(tr.cur) >= 0;
@@ -624,33 +681,10 @@ LR_D void trav_iteration(const TraversalStack &stack, const TravLane &tl, TravSt
     // (a lane at an inner node pushes at most three entries); if none can -- nearly always -- every push and pop of the
     // iteration is a bare LDS access instead of a compare + branch + access per entry (round 3: +1 %)
     const auto deep = lr_any(spb > tl.s_deep);
-    if (FUSED) {// (experiment LR_POOL_FUSED_FETCH: both gathers of the iteration requested up front, one wait; a lane the node step sends to a leaf tests it in the NEXT iteration)
-        const auto is_leaf = static_cast<int>(tr.cur) < static_cast<int>(kCurParked);
-        const auto any_inner = lr_any(is_inner);
-        prio_chain();
-        if (any_inner) { trav_node_fetch(stack, tl, tr, is_inner); }
-        // (the lanes that fetch no triangle never read one: their registers need a DEFINED value, not a particular one -- an empty asm "writes" them
-        // instead of the ten v_mov_b32 per iteration of `LeafTriangle tri{}`: 259 -> 250 VALU instructions in the pool loop, C2 1091 -> 1101, C3 1087 ->
-        // 1100, C4 1224 -> 1235 Msamples/s, films bit-identical now that trav_leaf_test's arithmetic is written out: profiles/r06zn_triangle_test_written_out.txt)
-        LeafTriangle tri;
-        asm volatile("" : "=v"(tri.a.x), "=v"(tri.a.y), "=v"(tri.a.z), "=v"(tri.a.w), "=v"(tri.b.x), "=v"(tri.b.y), "=v"(tri.b.z), "=v"(tri.b.w),
-                          "=v"(tri.c.x), "=v"(tri.c.y), "=v"(tri.c.z), "=v"(tri.c.w));
-        if (is_leaf) { tri = trav_leaf_fetch(tl, tr.cur); }
-        LR_MARK(kProbeIssue);
-        prio_tests();
-        trav_fetch_wait();
-        LR_MARK(kProbeVmWait);
-        LR_PIN2(tri.a.x, tri.b.x, tri.c.x, tri.c.w);
-        if (is_leaf) {
-            if (trav_leaf_test<COUNT, ALPHA>(tr, tr.cur, tri, stats)) { spb = tl.lds_base; }
-            if (!ALPHA || !(tr.phase & kPhasePendingAlpha)) { tr.cur = trav_pop(stack, tl, spb, deep); }
-            else { tr.cur |= kCurParkBit; }
-        }
-        LR_MARK2(kProbeLeaf, tr.cur, spb);
-        if (any_inner) { trav_node_step<COUNT, true>(stack, tl, tr, spb, inv, is_inner, deep, stats); }
-#if defined(LR_STALL_PROBE) && LR_STALL_PROBE < 2
-        LR_MARK(kProbeChain, tr.cur, spb);// (level 1: everything of the walk behind the wait -- triangle test, slab tests, sort, pushes / pops)
-#endif
+    if (FUSED) {// (LR_POOL_FUSED_FETCH: both gathers of the iteration requested up front, one wait)
+        LeafRequest rq;
+        const auto any_inner = trav_requests<COUNT, false>(stack, tl, tr, rq, true, stats);
+        trav_consume<COUNT, ALPHA>(stack, tl, tr, spb, inv, rq, any_inner, deep, stats);
         return;
     }
     if (lr_any(is_inner)) { trav_node_step<COUNT>(stack, tl, tr, spb, inv, is_inner, deep, stats); }

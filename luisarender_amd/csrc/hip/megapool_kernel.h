@@ -89,6 +89,21 @@ namespace lrd {
 #ifndef LR_POOL_FUSED_ALPHA
 #define LR_POOL_FUSED_ALPHA 0// (the ALPHA pool kernels under the fused flow: see above)
 #endif
+#ifndef LR_POOL_EARLY_FETCH
+// EARLY FETCH (fused flow only).  The end of an iteration -- the votes on ended rays, the turnover of LR_POOL_TURNOVER_LANES of them (19 v_swap_b32,
+// ctx_start, three v_rcp), the exit tests -- used to stand between the node step and the next iteration's requests, with nothing of the wave in
+// flight.  It changes nothing that the requests read: 1 = pool_trace sends an iteration's requests (dev_trace.h: trav_requests) right behind the
+// node step of the one before and runs the tail while they are on their way; 2 = only the four packet loads go early, the leaf lanes' triangles are
+// requested behind the tail (their twelve registers are not live across it); 0 = the round 5-6 order.  See pool_trace for why the requested packets
+// are the right ones.  Same instructions, same order of every lane's arithmetic: films and counters are bit-identical (tests/test_gpu_early_fetch.py).
+// Against the commit before, same box, runs alternating (profiles/early_fetch_ab_c2.txt): C2 1132.6 -> 1188.3 Msamples/s (+4.9 %, the runs of a side
+// 0.06 % apart), C3 1125 -> 1173, C4 1262 -> 1295, C2 under PaddedSobol 1039 -> 1086; 2 (packets only): 1149; the loop's census 426 -> 421 instructions,
+// 246 VALU on both sides, <4096> still at 128 VGPRs without a spill.
+#define LR_POOL_EARLY_FETCH 1
+#endif
+#ifndef LR_POOL_EARLY_TAIL_PRIO
+#define LR_POOL_EARLY_TAIL_PRIO 3// the tail behind the early requests stays at the chain's priority (dev_trace.h: WAVE PRIORITIES); 0: it runs at the tests' priority (C2 1188 -> 1178)
+#endif
 #ifndef LR_POOL_STATE_LEAN
 #define LR_POOL_STATE_LEAN 1
 #endif
@@ -156,6 +171,23 @@ LR_D void ctx_swap(PathCtx &a, PathCtx &b) {
     swap_words(a.tri, b.tri), swap_words(a.u, b.u), swap_words(a.v, b.v), swap_words(a.flags, b.flags);
 }
 
+// The exchange at a TURNOVER inside the traversal loop (pool_trace): `a` has just completed its job, `b` waits with rays.  Of the context that leaves
+// only what the shading block reads of a traced job is live -- the segment (no, nd), the hit (tri, u, v; read only if the job held a closest-hit ray,
+// and written where that ray ends), the flags -- and the hit of the one that arrives is dead: twelve of the nineteen words are copies under the same
+// EXEC, not exchanges.  C2 1190.1 -> 1197.9 Msamples/s (+0.65 %, a side's runs 0.02 % apart), films bit-identical (profiles/early_fetch_full_line.txt);
+// 0 restores the nineteen v_swap_b32.
+#ifndef LR_POOL_TURNOVER_MOVES
+#define LR_POOL_TURNOVER_MOVES 1
+#endif
+LR_D void ctx_turnover(PathCtx &a, PathCtx &b) {
+    if (LR_POOL_TURNOVER_MOVES == 0) { ctx_swap(a, b); return; }
+    a.so = b.so, a.sd = b.sd, a.s_tmax = b.s_tmax, a.n_tmin = b.n_tmin, a.n_tmax = b.n_tmax;
+    b.tri = a.tri, b.u = a.u, b.v = a.v;
+    swap_words(a.no.x, b.no.x), swap_words(a.no.y, b.no.y), swap_words(a.no.z, b.no.z);
+    swap_words(a.nd.x, b.nd.x), swap_words(a.nd.y, b.nd.y), swap_words(a.nd.z, b.nd.z);
+    swap_words(a.flags, b.flags);
+}
+
 LR_D uint32_t lane_rank(unsigned long long mask) {// lanes of `mask` below this one
     return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32u), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
 }
@@ -189,9 +221,22 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
     auto spb = tl.spb_of(tr.sp);
     if (tr.phase == kPhaseIdle) { tr.cur = kCurIdle; }// (inside the loop a lane's state is read off `cur`: dev_trace.h, TravLane)
     auto for_alpha = false;// (ALPHA: the wave leaves for the alpha tests of its parked candidates and comes straight back)
+    constexpr bool FUSED = LR_POOL_FUSED_FETCH != 0 && (!ALPHA || LR_POOL_FUSED_ALPHA != 0);
+    constexpr int EARLY = FUSED ? LR_POOL_EARLY_FETCH : 0;
 #ifdef LR_STALL_PROBE
     if (COUNT) { probe_start(stats); }
 #endif
+    // EARLY: the requests of the loop's first iteration; every later iteration's are sent from the one before.
+    // WHY THE REQUESTED PACKET / TRIANGLE IS THE ONE THE LANE CONSUMES.  trav_requests reads `cur` only: a lane at an inner node asks for cur's
+    // packet, a lane at a leaf for cur's triangle, every other lane (ended: kInvalid, idle: kCurIdle) for packet 0.  Between the requests and the
+    // next trav_consume runs the tail below, and it writes the `cur` of ENDED lanes only: to kCurIdle (asks for nothing) or, through ctx_start, to 0
+    // -- the root, the packet that lane's quad has just requested for it.  1 / d and the stack pointer of such a lane are made by the turnover,
+    // but they are inputs of trav_consume, not of the requests.  The packet loads go out in EVERY iteration, also when no lane stands at an inner node
+    // (trav_requests<.., ALWAYS>): a turnover may start rays in such a wave, too.  The counting kernels check every lane in every iteration
+    // (early_fetch_broken -> lrhip_counters::probe[kProbeEarlyFetchBroken], which must stay 0).
+    LeafRequest rq;
+    [[maybe_unused]] auto asked = tr.cur;// (counting kernels: what the lane's requests were made for)
+    if (EARLY != 0) { trav_requests<COUNT, true>(stack, tl, tr, rq, EARLY == 1, stats); }
     for (;;) {
         LR_MARK(kProbeTail, tr.cur);// (dev_trace.h, THE STALL PROBE: what the end of the previous iteration took)
         if (COUNT) {
@@ -203,7 +248,21 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
 #ifdef LR_TRACE_PROBE// (section cycles of the loop in the counting build: the iteration's walk -> nodes_empty, end of iteration -> trace_steps_starved; lane 0 reports)
         const auto probe_t0 = __builtin_readcyclecounter();
 #endif
-        trav_iteration<COUNT, ALPHA, LR_POOL_FUSED_FETCH != 0 && (!ALPHA || LR_POOL_FUSED_ALPHA != 0)>(stack, tl, tr, spb, inv, stats);
+        if (EARLY != 0) {
+            if (COUNT) {
+                const auto same = tr.cur == asked || (asked == kInvalid && (tr.cur == 0u || tr.cur == kCurIdle));
+                const auto leaf = EARLY != 1 || rq.at_leaf == (static_cast<int>(tr.cur) < static_cast<int>(kCurParked));// (the triangle on its way is a leaf lane's)
+                stats.early_fetch_broken += same && leaf ? 0u : 1u;
+            }
+            if (EARLY == 2) { trav_leaf_requests(tl, tr, rq); }
+            const auto any_inner = lr_any(static_cast<int>(tr.cur) >= 0), deep = lr_any(spb > tl.s_deep);// (from the lanes' state BEHIND the tail)
+            trav_consume<COUNT, ALPHA>(stack, tl, tr, spb, inv, rq, any_inner, deep, stats);
+            trav_requests<COUNT, true>(stack, tl, tr, rq, EARLY == 1, stats);
+            if (LR_POOL_EARLY_TAIL_PRIO == 0) { prio_tests(); }
+            if (COUNT) { asked = tr.cur; }
+        } else {
+            trav_iteration<COUNT, ALPHA, FUSED>(stack, tl, tr, spb, inv, stats);
+        }
 #ifdef LR_TRACE_PROBE
         const auto probe_t1 = __builtin_readcyclecounter();
         const auto probe_t2 = probe_t1;
@@ -230,7 +289,7 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
             tr.phase = kPhaseIdle, tr.cur = kCurIdle;
             if ((cur.flags & kCtxRays) == 0u) {// the job is complete: on to the other context's, if it waits with one
                 cur.flags |= kCtxDone;
-                if ((oth.flags & kCtxRays) != 0u) { ctx_swap(cur, oth); }
+                if ((oth.flags & kCtxRays) != 0u) { ctx_turnover(cur, oth); }
             }
             if ((cur.flags & kCtxRays) != 0u) {
                 ctx_start(cur, tr);
@@ -243,6 +302,9 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
         if (lr_ballot(tr.cur != kCurIdle) == 0ull) { break; }
         if (pool_shade_due(tr.phase, cur.flags, oth.flags, samples_left)) { break; }
     }
+    // EARLY: the wave leaves with requests in flight -- packets on their way into the staging area, which the shading block is about to use for
+    // parking.  They are waited for here, once per call, and dropped: the next call asks again (one request in ~25 iterations is wasted).
+    if (EARLY != 0) { trav_fetch_wait(); }
     LR_MARK(kProbeTail, tr.cur);
     prio_shade();
     tr.sp = tl.sp_of(spb);
@@ -927,6 +989,9 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
             if (lane == 0u) { local.trace_cycles += __builtin_readcyclecounter() - t_trace; }
             local.nodes_visited += ts.nodes, local.tris_tested += ts.tris, local.nodes_empty += ts.nodes_empty;
             local.trace_steps += ts.steps, local.trace_steps_busy += ts.steps_busy, local.trace_steps_starved += ts.steps_starved;
+#ifndef LR_STALL_PROBE// (the probe words are the stall probe's in its own build and zero otherwise: the last one reports a broken early fetch)
+            if (ts.early_fetch_broken != 0u) { atomicAdd(&args.counters->probe[kProbeEarlyFetchBroken], static_cast<unsigned long long>(ts.early_fetch_broken)); }
+#endif
         }
     }
     flush_tile();// the last item's tile

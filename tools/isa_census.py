@@ -98,7 +98,11 @@ def main():
     whole = [i for i, o in enumerate(ops) if o]
     census(whole[0], whole[-1], "whole object")
     if fetch:
-        enclosing = sorted([(hi - lo, lo, hi) for lo, hi in loops if lo <= fetch[0] and hi >= fetch[-1]])
+        # (an iteration = the packet requests AND the reads of the staged packets.  A kernel that requests an iteration's packets from the iteration
+        # before has a second group of four in front of the loop, and a backward branch into an out-of-line block is not a loop of its own)
+        staged = [i for i, o in enumerate(ops) if o and o[0].startswith("ds_read_b128")]
+        enclosing = sorted([(hi - lo, lo, hi) for lo, hi in loops if sum(lo <= f <= hi for f in fetch) >= 4 and any(lo <= r <= hi for r in staged)])
+        fetch = [f for f in fetch if enclosing and enclosing[0][1] <= f <= enclosing[0][2]]
         if enclosing:
             _, lo, hi = enclosing[0]
             census(lo, hi, "traversal loop (one wave-level iteration: node step + leaf step + bookkeeping)")
