@@ -27,7 +27,8 @@ HIPDIR := luisarender_amd/csrc/hip
 HOST_SRC := $(HOSTDIR)/sdl.cpp $(HOSTDIR)/scene.cpp $(HOSTDIR)/mesh_io.cpp $(HOSTDIR)/subdiv.cpp $(HOSTDIR)/catmull_clark.cpp $(HOSTDIR)/image_io.cpp $(HOSTDIR)/image_codecs.cpp $(HOSTDIR)/environment.cpp \
             $(HOSTDIR)/accel.cpp $(HOSTDIR)/host_api.cpp $(HOSTDIR)/luisa_render_shim.cpp
 HOST_HDR := $(wildcard $(HOSTDIR)/*.h) $(wildcard include/*.h)
-HIP_SRC := $(HIPDIR)/lrhip.hip
+# the host sources of liblrhip.so, one object each (lrhip_internal.h: which holds what); the kernels: megapath_variant.hip, heavy_variant.hip
+HIP_SRC := $(wildcard $(HIPDIR)/lrhip_*.hip)
 HIP_HDR := $(wildcard $(HIPDIR)/*.h) $(wildcard include/*.h)
 
 .PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly
@@ -51,21 +52,18 @@ oracle/liboracle.so: oracle/oracle.cpp $(wildcard oracle/*.h) include/lr_scene.h
 oracle/liboracle_fma.so: oracle/oracle.cpp $(wildcard oracle/*.h) include/lr_scene.h Makefile
 	$(CXX) $(ORACLE_FLAGS) -ffp-contract=fast -shared -o $@ oracle/oracle.cpp
 
-# The megakernel is precompiled for a curated set of feature masks (csrc/hip/variants.h), one object per mask so
-# that they build in parallel (make -j).  VARIANT_MASKS may be narrowed for experiments (a missing variant is a
-# run-time error of lrhip_render, never a fallback).
-VARIANT_MASKS ?= 0 1 2 3 4 5 6 7 8 9 10 11 12 13 14 15 16 17 18 19 20 21 22 23 60 61 62 63 124 125 126 127 636 637 638 639 252 253 254 255 256 257 258 259 \
-                 1024 1025 1026 1027 1028 1029 1030 1031 1032 1033 1034 1035 1036 1037 1038 1039 \
-                 3072 3073 3074 3075 3076 3077 3078 3079 3080 3081 3082 3083 3084 3085 3086 3087 \
-                 4096 4097 4098 4099 4100 4101 4102 4103 4104 4105 4106 4107 4108 4109 4110 4111 4112 4113 4114 4115 4116 4117 4118 4119 \
-                 5120 5121 5122 5123 5124 5125 5126 5127 5128 5129 5130 5131 5132 5133 5134 5135 \
-                 7168 7169 7170 7171 7172 7173 7174 7175 7176 7177 7178 7179 7180 7181 7182 7183 \
-                 8208 8209 8210 8211 8212 8213 8214 8215 12304 12305 12306 12307 12308 12309 12310 12311 \
-                 20482 20483 20486 20487 20490 20491 20494 20495 20498 20499 20502 20503 28690 28691 28694 28695 \
-                 21506 21507 21514 21515 23554 23555 23562 23563 32892 32893 32894 32895
+# The megakernel is precompiled for a curated set of feature masks, one object per mask so that they build in parallel (make -j).
+# csrc/hip/variants.h is the only place where the masks are written: the lists are read off its X-macros with the host preprocessor.
+# VARIANT_MASKS may be narrowed for experiments (a missing variant is a run-time error of lrhip_render, never a fallback).
+variants_h_list = $(shell echo '$(1)(X)' | $(CXX) -E -P -x c++ -include $(HIPDIR)/variants.h '-DX(mask)=mask' -)
+ifeq ($(origin VARIANT_MASKS),undefined)
+VARIANT_MASKS := $(call variants_h_list,LR_MEGAKERNEL_LIST)
+endif
 # the heavy-closure kernels of wavefront mode (csrc/hip/heavy_kernel.h; mask: 1 counters, 2 generic sampler, 4 Mix / 8 Layered instead of
 # Disney, 512 nested Mix / Layered)
-HEAVY_MASKS ?= 0 1 2 3 4 5 6 7 8 9 10 11 516 517 518 519 520 521 522 523
+ifeq ($(origin HEAVY_MASKS),undefined)
+HEAVY_MASKS := $(call variants_h_list,LR_HEAVY_LIST)
+endif
 OBJDIR := $(LIBDIR)/obj
 VARIANT_OBJ := $(foreach m,$(VARIANT_MASKS),$(OBJDIR)/variant_$(m).o) $(foreach m,$(HEAVY_MASKS),$(OBJDIR)/heavy_$(m).o)
 
@@ -90,7 +88,9 @@ VPT_HIPFLAGS ?= --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -ffp-contract=o
 # flag), but the same was true of <124> for two rounds.  Cost, same box: C2 782.3 -> 777.0, C3 809.6 -> 803.4, C4 875.6 -> 876.2
 # Msamples/s at 64 spp, films bit-identical (profiles/r04_ab_call_safe_lean.txt).
 CALL_SAFE_FLAGS ?= -mllvm -amdgpu-spill-sgpr-to-vgpr=0
-variant_flags = $(if $(filter 256 257 258 259,$(1)),$(VPT_HIPFLAGS),$(HIPFLAGS)) $(CALL_SAFE_FLAGS)
+# (the choice follows the kFeatVpt bit, 256, by design: whatever mask instantiates the volumetric kernel -- megapath_variant.hip tests the
+# same bit -- takes its arithmetic; today these are 256-259)
+variant_flags = $(if $(filter-out 0,$(shell echo $$(( $(1) & 256 )))),$(VPT_HIPFLAGS),$(HIPFLAGS)) $(CALL_SAFE_FLAGS)
 $(OBJDIR)/variant_%.o: $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(call variant_flags,$*) -DLR_VARIANT=$* -c -o $@ $(HIPDIR)/megapath_variant.hip
@@ -99,10 +99,11 @@ HEAVY_DEFS ?=
 $(OBJDIR)/heavy_%.o: $(HIPDIR)/heavy_variant.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(CALL_SAFE_FLAGS) $(HEAVY_DEFS) -DLR_HVARIANT=$* -c -o $@ $(HIPDIR)/heavy_variant.hip
-$(OBJDIR)/lrhip.o: $(HIP_SRC) $(HIP_HDR) Makefile
+HIP_OBJ := $(patsubst $(HIPDIR)/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
+$(HIP_OBJ): $(OBJDIR)/%.o: $(HIPDIR)/%.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $(HIP_SRC)
-$(LIBDIR)/liblrhip.so: $(OBJDIR)/lrhip.o $(VARIANT_OBJ)
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+$(LIBDIR)/liblrhip.so: $(HIP_OBJ) $(VARIANT_OBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -o $@ $^
 
 # experimental kernel builds for A/B runs on the GPU box:
@@ -112,7 +113,7 @@ hip-variant:
 	@mkdir -p $(VOBJDIR)
 	$(MAKE) --no-print-directory OBJDIR=$(VOBJDIR) HIPFLAGS='$(HIPFLAGS) $(DEFS)' VARIANT_MASKS='$(VARIANT_MASKS)' HEAVY_MASKS='$(HEAVY_MASKS)' \
 	    LIBDIR_OUT=$(LIBDIR)/variants/liblrhip_$(NAME).so variant-lib
-variant-lib: $(OBJDIR)/lrhip.o $(VARIANT_OBJ)
+variant-lib: $(HIP_OBJ) $(VARIANT_OBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -o $(LIBDIR_OUT) $^
 
 # The lean kernel <0> / <1> once more with the oracle's arithmetic (no fp contraction, correctly rounded division / sqrt, exact

@@ -188,7 +188,8 @@ int lrhip_work_items(uint32_t width, uint32_t height, uint32_t spp, uint32_t bal
  * frame and the caller's hint only, like the work items, so that films stay bit-identical under sharding and whatever memory is
  * free; a call over more tiles than the queues can hold takes them group after group, which changes no bit.
  *   mode         0 = automatic (default), 1 = never: the all-in-one megakernel variants (A/B, tests),
- *                2 = automatic with queues of eight tiles (tests: the tile groups a GPU short of memory would use)
+ *                2 = automatic with queues of seven tiles (the slots of eight, less the hand-over margin of an eighth of a slice's paths;
+ *                tests: the tile groups a GPU short of memory would use)
  *                Round 6: a slice runs ONE round and HANDS the paths still parked OVER to the next slice's first round (they are
  *                independent of their slice and add to the frame's order-independent fixed-point sums; the call's last slice runs all its
  *                rounds) -- its remaining rounds moved a few thousand paths each at one batch's latency, 6 % of a kitchen-class frame.
@@ -237,6 +238,32 @@ uint64_t lrhip_packed_texels(lrhip_ctx *ctx); /* texels of the uploaded scene he
 /* The automatic rule's threshold (no device needed): the number of BVH triangles from which a scene whose integrator allows paths of
  * `max_depth` vertices and whose description asks for `scene_spp` samples per pixel (0 = unknown) renders on the pool kernels.       */
 uint32_t lrhip_pool_auto_triangles(uint32_t max_depth, uint32_t scene_spp);
+
+/* TEST HOOK (no device needed, the product path never calls it): the selection rule of lrhip_render -- which kernels a call of a scene
+ * runs on -- for one point of its input space.
+ *   features        what the uploaded scene needs: LRHIP_FEAT_ENVIRONMENT .. LRHIP_FEAT_LAYERED, LRHIP_FEAT_NESTED, and the integrator class
+ *                   (none: MegaPath; LRHIP_FEAT_AUX_INTEGRATORS / LRHIP_FEAT_VOLUMETRIC / LRHIP_FEAT_AOV, each as lrhip_upload_scene sets it)
+ *   force_features  lrhip_set_diagnostics
+ *   flags           LRHIP_PLAN_FLAG_*: the call gathers counters; Combined environments nested in each other; the scene holds packed 8-bit texels;
+ *                   the scheduler wants the pool kernels (lrhip_set_scheduler, lrhip_pool_auto_triangles); the fixed-point film can hold the call
+ *   sampler_kind    LR_SAMPLER_*;  wf_mode: lrhip_set_wavefront;  max_depth: the integrator's
+ * out = { family LRHIP_FAMILY_*, mask of the main kernel (wavefront mode: of the camera pass), of the continuation pass, of the heavy kernels
+ * of Disney / Mix / Layered (their own numbering: bit 0 counters, 1 generic sampler, 4 Mix, 8 Layered, 512 nested), whether the film is
+ * summed in fixed point, whether lrhip_upload_scene packs such a scene's texels at all }; masks that do not apply are 0xffffffff.
+ * LRHIP_ERROR_UNSUPPORTED (out still filled) when a kernel of the plan is not compiled into this library.                              */
+#define LRHIP_FAMILY_NONE 0u      /* no compiled feature set covers the scene */
+#define LRHIP_FAMILY_LANE 1u      /* one path per lane, float film */
+#define LRHIP_FAMILY_POOL 2u
+#define LRHIP_FAMILY_WAVEFRONT 3u
+#define LRHIP_FAMILY_AOV 4u
+#define LRHIP_PLAN_FLAG_COUNTERS 1u
+#define LRHIP_PLAN_FLAG_ENV_TREE 2u
+#define LRHIP_PLAN_FLAG_PACKED_TEXELS 4u
+#define LRHIP_PLAN_FLAG_WANTS_POOL 8u
+#define LRHIP_PLAN_FLAG_FIXED_FITS 16u
+#define LRHIP_PLAN_WORDS 8
+int lrhip_plan_kernels(uint32_t features, uint32_t force_features, uint32_t flags, uint32_t sampler_kind, uint32_t wf_mode, uint32_t max_depth,
+                       uint32_t out[LRHIP_PLAN_WORDS]);
 
 const char *lrhip_last_error(void);
 

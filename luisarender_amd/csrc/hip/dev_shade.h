@@ -381,7 +381,7 @@ LR_D float pow_nonpositive(float c, float g) {
 }
 // EIGHT-BIT TEXELS STAY EIGHT BITS ON THE DEVICE (round 5).  The host decodes every image to float RGBA (what the reference's textures hold
 // and what the oracle reads); an image whose every texel is an 8-bit code's float -- a PNG / JPEG / BMP / TGA albedo or roughness map --
-// is uploaded as one 32-bit word per texel instead of sixteen bytes (lrhip.hip: pack_byte_textures), behind the float texels in the same
+// is uploaded as one 32-bit word per texel instead of sixteen bytes (lrhip_tables.hip: pack_byte_textures), behind the float texels in the same
 // buffer, and decoded here to EXACTLY the floats the host made: `pad` bits 0-1 say how the host converted (1: b * (1 / 255.f), the PNG
 // reader; 2: b / 255.f, the other readers -- byte_over_255 below, checked against the division for all 256 codes at upload), bits 4-7
 // mark channels that hold ONE value over the whole image (a padded alpha of 1: lr_texture::v carries it).  A quarter of the
@@ -970,7 +970,7 @@ LR_CALL EnvSample env_sample_one(EnvTables tb, const DEnvironment *envp, f2 u) {
 
 // Combined nodes nested in each other (combined.cpp composes freely; device code has no recursion): the tree is walked with an
 // explicit stack, in the reference's operation order (post-order: a.L * scale_a + b.L * scale_b, the pdfs interpolated), by out-of-line
-// functions that only the variants which make real calls anyway hold (lrhip.hip picks one for such a scene) -- the lean kernels' register
+// functions that only the variants which make real calls anyway hold (lrhip_kernels.hip picks one for such a scene) -- the lean kernels' register
 // allocation never sees them.  At most LR_ENV_MAX_COMBINED_DEPTH Combined nodes on a path (lr_scene.h; checked at upload).
 #if defined(LR_VARIANT) && ((LR_VARIANT) & (96 | 256))
 #define LR_ENV_TREE 1

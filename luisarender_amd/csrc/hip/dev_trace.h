@@ -345,7 +345,7 @@ LR_D void trav_slab_sort_q(float4 q0, float4 q1, float4 q2, const TravState &tr,
     // packet: q0 = (origin.xyz, scale.x)  q1 = (lo_x4, lo_y4, lo_z4, hi_x4) bytes
     //         q2 = (hi_y4, hi_z4, scale.y, scale.z)  q3 = child[4]
     // An EMPTY slot has inverted planes (lo 255, hi 0) and names the scene's sentinel leaf (a triangle nothing hits,
-    // lrhip.hip: quantise_node), so it needs no test of its own: it fails the slab test wherever the node has an extent
+    // lrhip_tables.hip: quantise_node), so it needs no test of its own: it fails the slab test wherever the node has an extent
     // and costs one wasted triangle test where it has none.
     auto ax = q0.w * inv.x, ay = q2.z * inv.y, az = q2.w * inv.z;
     auto bx = (q0.x - tr.o.x) * inv.x, by = (q0.y - tr.o.y) * inv.y, bz = (q0.z - tr.o.z) * inv.z;

@@ -104,7 +104,7 @@ struct WfQueue {
     uint32_t *base;
     uint32_t capacity;
     // field-major columns: a column's address is wave-uniform (SGPRs), the slot a 32-bit byte offset on top of it (capacity <= 2^30,
-    // lrhip.hip) -- one global access with scalar base per field instead of 64-bit address arithmetic per field and lane
+    // lrhip_wavefront.hip) -- one global access with scalar base per field instead of 64-bit address arithmetic per field and lane
     LR_D uint32_t *at(uint32_t slot, uint32_t field) const {
         return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(base + static_cast<size_t>(field) * capacity) + (slot << 2u));
     }

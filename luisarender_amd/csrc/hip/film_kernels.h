@@ -1,5 +1,5 @@
 // film_kernels.h — the small kernels around the megakernel: chunk resolve and the Color film's convert
-// (src/films/color.cpp:87-93).  Included by lrhip.hip only (the megakernel variants are separate objects).
+// (src/films/color.cpp:87-93).  Included by lrhip_context.hip only (the megakernel variants are separate objects).
 #pragma once
 #include "dev_scene.h"
 

@@ -1,5 +1,6 @@
 // heavy_variant.hip — ONE instantiation of the heavy-closure kernel of wavefront mode (heavy_kernel.h) and its launch / occupancy
-// entry points for lrhip.hip.  LR_HVARIANT: bit 0 diagnostics counters, bit 1 generic sampler, bits 2-3 the closure kind (0 Disney,
+// entry points for the kernel table (lrhip_kernels.hip; `lds_bytes`: the table's common signature, 0 here).  LR_HVARIANT: bit 0 diagnostics
+// counters, bit 1 generic sampler, bits 2-3 the closure kind (0 Disney,
 // 4 Mix, 8 Layered), bit 9 (512) Mix / Layered nested in each other (Mix / Layered kernels only).  One object per mask, built in
 // parallel like the megakernel variants.
 #include <hip/hip_runtime.h>
@@ -25,11 +26,12 @@ template __global__ void heavy_kernel<LR_HFEATURES, LR_HKIND>(DScenePtr, RenderA
 }
 
 extern "C" hipError_t LR_CAT(lrhip_heavy_launch_, LR_HVARIANT)(unsigned blocks, hipStream_t stream, const lrd::DScene *device_scene,
-                                                              const lrd::RenderArgs *args) {
-    hipLaunchKernelGGL((lrd::heavy_kernel<LR_HFEATURES, LR_HKIND>), dim3(blocks), dim3(lrd::kBlockThreads), 0, stream, (lrd::DScenePtr)device_scene, *args);
+                                                              const lrd::RenderArgs *args, unsigned lds_bytes) {
+    hipLaunchKernelGGL((lrd::heavy_kernel<LR_HFEATURES, LR_HKIND>), dim3(blocks), dim3(lrd::kBlockThreads), lds_bytes, stream,
+                       (lrd::DScenePtr)device_scene, *args);
     return hipGetLastError();
 }
 
-extern "C" hipError_t LR_CAT(lrhip_heavy_occupancy_, LR_HVARIANT)(int *blocks_per_cu) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, lrd::heavy_kernel<LR_HFEATURES, LR_HKIND>, lrd::kBlockThreads, 0);
+extern "C" hipError_t LR_CAT(lrhip_heavy_occupancy_, LR_HVARIANT)(int *blocks_per_cu, unsigned lds_bytes) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, lrd::heavy_kernel<LR_HFEATURES, LR_HKIND>, lrd::kBlockThreads, lds_bytes);
 }

@@ -1,0 +1,195 @@
+// lrhip_internal.h — what the host sources of liblrhip.so share behind include/lrhip.h: the context, device buffers, error reporting, the
+// nominal-grid constants, the kernel table and the selection rule's declarations.  The sources, by responsibility:
+//   lrhip_context.hip    context, setters, film binding / download, counters; the small film kernels (film_kernels.h) and their launchers
+//   lrhip_tables.hip     host-side checks and tables of an upload: index validation, 8-bit texel packing, the time-dependent tables
+//   lrhip_upload.hip     lrhip_upload_scene (in named steps) / lrhip_update_scene
+//   lrhip_kernels.hip    the table of compiled kernels (variants.h), the selection rule (plan_kernels), occupancy
+//   lrhip_render.hip     work items, fixed-point film, lrhip_render (one path per lane, pool, AOV)
+//   lrhip_wavefront.hip  the host loop of wavefront mode
+//   lrhip_comm.hip       the RCCL collectives
+// Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
+#pragma once
+#include "../../../include/lrhip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "megapath_kernel.h"
+#include "megapool_kernel.h"
+#include "variants.h"
+
+namespace lrh {
+
+int fail(int code, const std::string &msg);// sets the thread's lrhip_last_error text (lrhip_context.hip), returns `code`
+
+#define LR_HIP_CHECK(expr)                                                                                   \
+    do {                                                                                                     \
+        auto err_ = (expr);                                                                                  \
+        if (err_ != hipSuccess) {                                                                            \
+            return lrh::fail(LRHIP_ERROR_DEVICE, std::string{#expr} + ": " + hipGetErrorString(err_));       \
+        }                                                                                                    \
+    } while (0)
+
+struct DeviceBuffer {
+    void *ptr{nullptr};
+    size_t bytes{0};
+    void release() {
+        if (ptr != nullptr) { (void)hipFree(ptr); }
+        ptr = nullptr, bytes = 0;
+    }
+};
+int ensure(DeviceBuffer &b, size_t bytes);// grows, never shrinks; the contents are lost when it grows
+
+// persistent-grid sizing inputs that must not depend on the device actually present, so that the
+// chunking (and therefore the fp32 summation order of the film) is identical on every GPU
+constexpr double kNominalWaves = 4096.0;// 256 CUs x 4 SIMDs x 4 waves
+constexpr uint32_t kMaxChunks = 64u;     // partial planes: chunk_count x 16 B per pixel
+// wavefront mode: rounds of a slice before its parked paths wait for the next slice (film_kernels.h: wf_carry_kernel)
+constexpr uint32_t kWfCarryRounds = 1u;
+// bytes the queues of wavefront mode may take (of 288 GB; round 6: 104 GB -- the default slice with its hand-over margin takes 86 - 100)
+constexpr uint64_t kWfQueueBudget = 104ull << 30u;
+#ifndef LR_MAX_BLOCKS_PER_CU
+#define LR_MAX_BLOCKS_PER_CU 8
+#endif
+constexpr uint32_t kMaxBlocksPerCu = LR_MAX_BLOCKS_PER_CU; // resident 256-thread blocks per CU the persistent grid may use (-D: A/B builds)
+// channels per pixel of each AOV component (lr_scene.h: LR_AOV_*)
+constexpr uint32_t kAovChannels[LR_AOV_COMPONENTS] = {3u, 3u, 3u, 3u, 3u, 1u, 3u, 3u, 1u};
+
+// ---- the compiled kernels (lrhip_kernels.hip): one entry per mask of variants.h, megakernels (LR_MEGAKERNEL_LIST) first, then the
+// heavy-closure kernels of wavefront mode (LR_HEAVY_LIST, whose masks are a numbering of their own: `heavy`).  The entry points are weak,
+// so that experimental builds may leave kernels out (make hip-variant VARIANT_MASKS=...): a missing one is reported, never silently
+// replaced.
+struct KernelEntry {
+    uint32_t mask;
+    bool heavy;
+    hipError_t (*launch)(unsigned blocks, hipStream_t, const lrd::DScene *device_scene, const lrd::RenderArgs *, unsigned lds_bytes);
+    hipError_t (*occupancy)(int *blocks_per_cu, unsigned lds_bytes);
+};
+#define LR_COUNT_ONE(mask) +1u
+constexpr size_t kKernelCount = 0u LR_MEGAKERNEL_LIST(LR_COUNT_ONE) LR_HEAVY_LIST(LR_COUNT_ONE);
+#undef LR_COUNT_ONE
+extern const KernelEntry kKernels[kKernelCount];
+// the entry of a mask whose entry points are in the loaded library; nullptr: not compiled into it
+const KernelEntry *find_kernel(uint32_t mask, bool heavy = false);
+
+// ---- the selection rule (lrhip_kernels.hip: plan_kernels), the one place that decides which kernels a call runs on
+struct PlanInputs {
+    // lrhip_ctx::features: the scene's lrd::kFeat* bits, with the integrator class (kFeatAux / kFeatVpt / kFeatAov) and kFeatNest
+    uint32_t features;
+    uint32_t force_features;// lrhip_set_diagnostics
+    uint32_t sampler_kind;  // LR_SAMPLER_*
+    uint32_t wf_mode;       // lrhip_set_wavefront
+    uint32_t max_depth;
+    bool count;             // LRHIP_RENDER_COUNTERS
+    bool env_tree;          // Combined environments nested in each other
+    bool byte_texels;       // the uploaded scene holds packed 8-bit texels
+    bool wants_pool;        // the scheduler's choice (lrhip_render.hip: wants_pool)
+    bool fixed_fits;        // the fixed-point film can hold this call (fixed_point_bits)
+};
+constexpr uint32_t kNoKernel = ~0u;
+struct KernelPlan {
+    uint32_t family;// LRHIP_FAMILY_*
+    uint32_t main;  // mask of the kernel that renders; wavefront mode: of the camera pass
+    uint32_t cont;  // wavefront mode: the continuation pass
+    uint32_t heavy[lrd::kWfKinds];// wavefront mode: the heavy kernel of each closure kind (LR_HEAVY_LIST numbering)
+    bool fixed_point;// the film is summed in 64-bit fixed point
+};
+KernelPlan plan_kernels(const PlanInputs &in);
+bool scene_kernels_decode_byte_texels(bool alpha_tested, bool mix_or_layered, bool env_tree, bool megapath);
+
+}// namespace lrh
+
+struct lrhip_ctx {
+    int device{0};
+    hipStream_t stream{nullptr};
+    bool own_stream{true};
+    hipEvent_t ev_begin{nullptr}, ev_end{nullptr};
+    bool timed{false};
+    // 8-bit images as 8-bit texels on the device (lrhip_upload_scene): lrhip_set_texture_storage: 0 never, 1 = where the scene's float
+    // texels exceed kByteTextureFloatBytes, 2 always
+    uint32_t byte_textures{1u};
+    uint64_t packed_texel_words{0u};// texels of the uploaded scene held as 8-bit codes (lrhip_packed_texels)
+    uint64_t texel_bytes{0u};       // bytes of the texel table on the device (float texels of the images that stay float + the packed words)
+    bool in_split{false};        // lrhip_render is rendering a call in sample sub-ranges: the first sub-range's begin event stands for the call
+    std::vector<lrh::DeviceBuffer> scene_buffers;
+    lrd::DScene scene{};
+    bool scene_ready{false};
+    uint32_t width{0}, height{0};
+    float film_scale[3]{1.f, 1.f, 1.f};
+    lrh::DeviceBuffer film_own, converted, partial, spill, counters, work_counter;
+    lrh::DeviceBuffer scene_record;// lrd::DScene in device memory: the kernels read it through scalar loads (dev_scene.h: DScenePtr)
+    float4 *film{nullptr};// bound film (own or external)
+    float4 *film_external{nullptr};// lrhip_bind_film's buffer; kept across uploads of the same resolution
+    uint32_t film_external_w{0}, film_external_h{0};
+    uint32_t grid_blocks{0};
+    uint32_t cu_count{0};
+    uint32_t bvh_depth{0};
+    uint32_t update_counts[7]{};// table sizes of the uploaded scene: what lrhip_update_scene checks its argument against
+    uint32_t last_variant{0u};// feature mask of the kernel the last lrhip_render launched
+    uint32_t features{0u};// lrd::kFeat* bits the uploaded scene needs (environment, alpha test, Disney / Mix / Layered)
+    bool env_tree{false};// Combined environments nested in each other: only the call-making variants walk them (dev_shade.h)
+    // resident blocks per CU of each kernel of kKernels, same index (-1: not asked yet; kernel_blocks).  lrhip_upload_scene resets it: the
+    // AOV kernels' LDS size depends on the uploaded scene
+    int kernel_blocks[lrh::kKernelCount];
+    uint32_t diag_force_features{0u};// lrhip_set_diagnostics (tests / tools)
+    double diag_item_scale{0.};
+    // wavefront mode (dev_scene.h: WfArgs): queues, counters and the fixed-point radiance sums; sized on first use
+    lrh::DeviceBuffer wf_heavy, wf_cont, wf_counts, wf_accum;
+    // lrhip_set_wavefront: 0 = automatic (scenes with Mix / Layered surfaces), 1 = never, 2 = automatic with tiny tile groups (tests)
+    uint32_t wf_mode{0u};
+    uint32_t wf_slice_paths{0u}; // paths per slice (queue capacity); 0 = default
+    // lrhip_set_diagnostics: rounds before a slice hands its parked paths over (0 = kWfCarryRounds; 65535 = never: every slice drains)
+    uint32_t diag_wf_carry_rounds{0u};
+    // round 4: the path-pool scheduler (megapool_kernel.h): slot records of every resident wave; lrhip_set_scheduler
+    lrh::DeviceBuffer pool;
+    // lrhip_set_scheduler: 0 = automatic (wants_pool), 1 = one path per lane, 2 = the pool kernels where one exists for the scene
+    uint32_t scheduler{0u};
+    // the AOV integrator: planar sums [channel][pixel] of the enabled components (lrd::DScene::aov) and the chunks' partial planes
+    lrh::DeviceBuffer aov, aov_partial;
+};
+
+namespace lrh {
+
+// resident blocks per CU of `entry` (asked once per upload, at most kMaxBlocksPerCu); `lds_bytes`: the launch's dynamic LDS
+int kernel_blocks(lrhip_ctx *ctx, const KernelEntry &entry, unsigned lds_bytes, uint32_t &blocks_per_cu);
+
+void release_scene(lrhip_ctx *ctx);// frees the uploaded scene's buffers and what is sized for it (queues, pool records)
+
+// lrhip_tables.hip: host-side checks and tables of an upload (empty string / empty error: fine)
+std::string validate_indices(const lr_scene *s);
+constexpr uint64_t kByteTextureFloatBytes = 192ull << 20u;// float texels of a scene's images from which lrhip_set_texture_storage mode 1 packs
+std::vector<uint32_t> pack_byte_textures(const lr_scene *s, std::vector<lr_texture> &textures);
+uint32_t bvh_depth(const lr_accel &accel);
+std::vector<lrd::DNodeQ> build_packed_nodes(const lr_scene *s);
+std::vector<uint8_t> build_padded_triangles(const lr_scene *s);
+std::vector<lrd::DInstance> build_instances(const lr_scene *s);
+std::vector<lrd::DShadeTri> build_shade_tris(const lr_scene *s, const std::vector<lrd::DInstance> &instances, std::string &error);
+void set_camera(lrd::DScene &d, const lr_scene *s);
+
+// lrhip_render.hip
+struct Chunking {
+    uint32_t count, big_count, big, small;
+};
+Chunking chunking_of(uint32_t spp, double shard_tiles, double item_scale, bool taper);
+int fixed_point_bits(float film_clamp, float shutter_weight, uint32_t spp);
+int ensure_accum(lrhip_ctx *ctx, uint32_t pixel_count);
+int ensure_pool(lrhip_ctx *ctx, uint32_t resident_blocks);
+// lrhip_wavefront.hip
+int render_wavefront(lrhip_ctx *ctx, const lrhip_render_params *p, const KernelPlan &plan, uint32_t tiles_x, uint32_t tiles_y,
+                     uint32_t tiles_in_range, uint32_t tile_count);
+
+// launchers of the film kernels (film_kernels.h, compiled into lrhip_context.hip), on the context's stream
+hipError_t launch_resolve_partial(lrhip_ctx *ctx, const float4 *partial, uint32_t chunk_count, uint32_t tiles_x, uint32_t tile_begin,
+                                  uint32_t tile_end, uint32_t tile_stride);
+hipError_t launch_resolve_aov_partial(lrhip_ctx *ctx, uint32_t chunk_count, uint32_t tiles_x, uint32_t tile_begin, uint32_t tile_end,
+                                      uint32_t tile_stride);
+hipError_t launch_wf_resolve(lrhip_ctx *ctx, double inv_scale);
+hipError_t launch_wf_carry(lrhip_ctx *ctx, uint32_t margin, uint32_t mode);
+
+}// namespace lrh

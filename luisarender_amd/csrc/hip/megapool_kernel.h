@@ -23,8 +23,8 @@
 //     scratch traffic evicted the BVH's top levels from the 32 KB vector L1, and a node step took 4200 cycles instead of 2100
 //     (HISTORY.md appendix, section 4.1c; profiles/archive/r04c_*, r04g_*).
 // Measured (profiles/r04_final_schedulers.txt, kernel time of the one-path-per-lane kernel / this one, same build, same box): C2 1.08
-// at 1024 spp, C3 1.18, C4 1.06, C5 (wavefront mode) 1.10 at 64 spp; a Cornell box 0.88 -- lrhip.hip: wants_pool picks this kernel
-// from ~100 thousand triangles up, earlier for deep paths at few samples per pixel, later for shallow ones (lrhip.hip: pool_auto_triangles; profiles/r05j_scheduler_sweep.txt).
+// at 1024 spp, C3 1.18, C4 1.06, C5 (wavefront mode) 1.10 at 64 spp; a Cornell box 0.88 -- lrhip_render.hip: wants_pool picks this kernel
+// from ~100 thousand triangles up, earlier for deep paths at few samples per pixel, later for shallow ones (lrhip_render.hip: pool_auto_triangles; profiles/r05j_scheduler_sweep.txt).
 //
 // MEASURED AND NOT KEPT (profiles/archive/r04a_*): 128 path SLOTS per wave shared by all lanes -- records of 128 B in global memory, ray and
 // shade queues of slot numbers in LDS, lanes fetching their next job from the ray queue inside the loop.  It filled the lanes (0.93 /
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                     // wavefront mode: a Disney / Mix / Layered surface is not shaded here (megapath_kernel.h): the path goes into the
                     // queue of its closure kind; heavy_kernel.h shades the vertex and hands the path back as a continuation record
                     if (WF && has_surface) {
-                        const auto heavy_kind = (it.flags >> 10u) & 3u;// (baked into the triangle's record: lrhip.hip, build_shade_tris)
+                        const auto heavy_kind = (it.flags >> 10u) & 3u;// (baked into the triangle's record: lrhip_tables.hip, build_shade_tris)
                         if (heavy_kind != 0u) { park_kind = heavy_kind - 1u, has_surface = false; }
                     }
                     if (WF) {// ---- park (at once: the hit and the direction die here instead of living through the closure code below -- 25 -> 15

@@ -1,6 +1,7 @@
-// variants.h — the precompiled megakernel feature masks: every entry of lrd::kSceneVariants (megapath_kernel.h)
-// x {counters} x {generic sampler}.  One object file each (megapath_variant.hip, -DLR_VARIANT=<mask>), built in
-// parallel by the Makefile (VARIANT_MASKS must list the same numbers).
+// variants.h — the precompiled kernels' feature masks, and the ONLY place where their numbers are written: the Makefile reads its object
+// lists off these macros with the host preprocessor (VARIANT_MASKS, HEAVY_MASKS), lrhip_kernels.hip builds the kernel table from them and
+// checks at compile time that every entry of lrd::kSceneVariants (megapath_kernel.h) x {counters} x {generic sampler} is listed.
+// One object file per mask (megapath_variant.hip, -DLR_VARIANT=<mask>; heavy_variant.hip, -DLR_HVARIANT=<mask>), built in parallel.
 #pragma once
 #define LR_VARIANT_LIST(X)                                                                  \
     X(0) X(1) X(2) X(3)         /* lean: Matte / Mirror / Glass / Plastic / Metal, lights */  \
@@ -34,7 +35,7 @@
 
 // round 6: the lean pool kernels once more with the generic sampler's kind fixed to PaddedSobol (kFeatPadded = 16384 | kFeatGeneric): plain,
 // environment, alpha, environment + alpha, Disney, environment + Disney, and the 8-bit-texel Disney sets, each with its counting twin.  Not part of
-// the kSceneVariants x {Count} x {Generic} grid: lrhip_render looks them up by mask (kPaddedVariants).  Measured (profiles/r06y_padded_sobol_kernels.txt,
+// the kSceneVariants x {Count} x {Generic} grid: the selection rule asks for them by mask (lrhip_kernels.hip: plan_kernels).  Measured (profiles/r06y_padded_sobol_kernels.txt,
 // r06za_padded_draws_out_of_line.txt, r06zf_padded_environment_set.txt): C2 949 -> 1004 Msamples/s at 256 spp, the camera class under PaddedSobol 1007 -> 1111,
 // the bedroom class 974 -> 1011.
 #define LR_PADDED_LIST(X) X(20482) X(20483) X(20486) X(20487) X(20490) X(20491) X(20494) X(20495) X(20498) X(20499) X(20502) X(20503) X(28690) X(28691) X(28694) X(28695) \
@@ -42,6 +43,13 @@
     X(21506) X(21507) X(21514) X(21515) X(23554) X(23555) X(23562) X(23563)
 
 // the AOV integrator (kFeatAov = 32768, src/integrators/aov.cpp): the all-closures scene mask with its counting and generic-sampler twins.
-// Not part of kSceneVariants: their launch takes the dynamic LDS of the enabled channels (megapath_variant.hip: lrhip_aov_launch_<mask>),
-// and lrhip_render asks for them by mask for AOV scenes only
+// Not part of kSceneVariants: their launch takes the dynamic LDS of the enabled channels (the `lds_bytes` of the launch entry points,
+// megapath_variant.hip), and the selection rule asks for them by mask for AOV scenes only
 #define LR_AOV_LIST(X) X(32892) X(32893) X(32894) X(32895)
+
+// every object built from megapath_variant.hip
+#define LR_MEGAKERNEL_LIST(X) LR_VARIANT_LIST(X) LR_PADDED_LIST(X) LR_AOV_LIST(X)
+
+// the heavy-closure kernels of wavefront mode (heavy_kernel.h; heavy_variant.hip, -DLR_HVARIANT=<mask>): bit 0 counters, bit 1 generic sampler,
+// bits 2-3 the closure kind (0 Disney, 4 Mix, 8 Layered), 512 Mix / Layered nested in each other
+#define LR_HEAVY_LIST(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(516) X(517) X(518) X(519) X(520) X(521) X(522) X(523)

@@ -322,7 +322,7 @@ struct oracle_ctx {
                          float2{bary.y, bary.z};
         // BAKED-GEOMETRY MODE (oracle_bvh.h: Accel::set_bake; test infrastructure): a traced hit is reconstructed from the fp32
         // world-space triangle the device intersected -- point, geometric normal, area, tangent and the interpolation of the
-        // world-space vertex normals in the device's own order (csrc/hip/dev_shade.h: reconstruct_baked, lrhip.hip: build_shade_tris)
+        // world-space vertex normals in the device's own order (csrc/hip/dev_shade.h: reconstruct_baked, lrhip_tables.hip: build_shade_tris)
         if (const auto bt = use_wo ? accel.baked(inst_id, prim_id) : nullptr; bt != nullptr) {
             auto b0 = f3(bt->v0[0], bt->v0[1], bt->v0[2]), e1 = f3(bt->e1[0], bt->e1[1], bt->e1[2]), e2 = f3(bt->e2[0], bt->e2[1], bt->e2[2]);
             p = b0 + e1 * bary.y + e2 * bary.z;

@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _variant(renderer):
-    """the frame's kernel variant without the scheduler bit (LRHIP_FEAT_POOL): which scheduler a scene gets is lrhip.hip: wants_pool's
+    """the frame's kernel variant without the scheduler bit (LRHIP_FEAT_POOL): which scheduler a scene gets is lrhip_render.hip: wants_pool's
     business (tests/test_gpu_pool.py holds the two against each other), which closures / traversal / sampler code it needs is these tests'"""
     return renderer.last_variant() & ~4096
 
@@ -1262,7 +1262,7 @@ def test_two_contexts_driven_from_two_host_threads_render_one_frame(tmp_path):
 
 def test_byte_texels_decode_to_the_floats_the_host_made(tmp_path):
     """lrhip_set_texture_storage (round 5): an image whose texels are 8-bit codes' floats stays 8 bits per channel on the device
-    (lrhip.hip: pack_byte_textures; dev_shade.h: texel_at).  The decode must give back exactly the floats the host readers made --
+    (lrhip_tables.hip: pack_byte_textures; dev_shade.h: texel_at).  The decode must give back exactly the floats the host readers made --
     b * (1 / 255.f) from the PNG reader, b / 255.f from the JPEG / BMP / TGA readers and from a PFM that holds byte / 255 -- so the
     film of storage mode 2 is the film of mode 0, bit for bit; a float picture that is no 8-bit code stays float."""
     from luisarender_amd.render import MegaPathRenderer

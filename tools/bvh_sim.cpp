@@ -37,7 +37,7 @@ static int g_t_bits = 32;// the entry distance is kept with this many of its top
 struct Hit { float t; uint32_t tri; float u, v; };
 
 // optional model of the device's 64-byte packets: child boxes snapped outwards to the 8-bit grid of their node's own box
-// (lrhip.hip: quantise_node); BVH_SIM_QUANTISED=1
+// (lrhip_tables.hip: quantise_node); BVH_SIM_QUANTISED=1
 static bool g_quantised = false;
 static std::vector<lr_bvh4_node> g_qnodes;
 static void quantise(const lr_accel &acc) {

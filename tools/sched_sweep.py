@@ -2,7 +2,7 @@
 """Where do the two schedulers of the lean kernels break even (GPU box)?  The room stand-in swept over its triangle count, the path depth
 and the samples per pixel -- the quantities that drive what the path pool buys (long walks, the drain of a launch) and what it costs (a
 costlier shading block) -- kernel time of the one-path-per-lane kernel, the pool kernel, and which of them lrhip_render's automatic rule
-(lrhip.hip: wants_pool) picks.  VERDICT r04 item 8: no configuration where the automatic choice is the slower one by more than noise.
+(lrhip_render.hip: wants_pool) picks.  VERDICT r04 item 8: no configuration where the automatic choice is the slower one by more than noise.
 
     python tools/sched_sweep.py [quick]
 """
