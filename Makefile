@@ -31,8 +31,8 @@ HOST_HDR := $(wildcard $(HOSTDIR)/*.h) $(wildcard include/*.h)
 HIP_SRC := $(wildcard $(HIPDIR)/lrhip_*.hip)
 HIP_HDR := $(wildcard $(HIPDIR)/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly
-all: host oracle hip cli ieee shallow noearly
+.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly nopair
+all: host oracle hip cli ieee shallow noearly nopair
 
 # oracle/_ref: the reference's OWN sources compiled in place against the scalar LuisaCompute stand-in of oracle/ref_shim
 # (test infrastructure: pins oracle/ to the reference; needs /root/reference, so only where the reference tree exists)
@@ -138,6 +138,13 @@ $(LIBDIR)/variants/liblrhip_shallow.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hi
 noearly: $(LIBDIR)/variants/liblrhip_noearly.so
 $(LIBDIR)/variants/liblrhip_noearly.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
 	$(MAKE) --no-print-directory hip-variant NAME=noearly DEFS='-DLR_POOL_EARLY_FETCH=0' VARIANT_MASKS='4096 4097 4100 4101' HEAVY_MASKS=
+
+# The lean pool kernels once more WITHOUT the leaf / node pairing of the traversal loop (megapool_kernel.h: LR_POOL_LEAF_NODE_PAIR): a lane at a
+# leaf spends the iteration on its triangle alone.  TEST INFRASTRUCTURE: the pairing regroups a lane's steps into wave iterations and nothing
+# else, so the shipped library's frames and its ray / node / triangle counters must equal this library's (tests/test_gpu_leaf_pair.py).
+nopair: $(LIBDIR)/variants/liblrhip_nopair.so
+$(LIBDIR)/variants/liblrhip_nopair.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
+	$(MAKE) --no-print-directory hip-variant NAME=nopair DEFS='-DLR_POOL_LEAF_NODE_PAIR=0' VARIANT_MASKS='4096 4097 4100 4101' HEAVY_MASKS=
 
 cli: $(BINDIR)/luisa-render-cli
 $(BINDIR)/luisa-render-cli: $(HOSTDIR)/cli.cpp $(HOSTDIR)/plugin_megapath.cpp $(LIBDIR)/liblrhost.so $(HOST_HDR)

@@ -312,12 +312,13 @@ LR_D uint32_t trav_pop(const TraversalStack &stack, const TravLane &tl, uint32_t
 // ---- node step of the WAVE (every lane calls; `is_inner` lanes test the packet of tr.cur): cooperative packet fetch, quantised slab
 // tests, near -> far ordering, pushes.  `deep`: some lane may reach the HBM overflow area of the stack in this iteration.
 // the fetch half of the node step: the packets of the lanes at inner nodes are on their way into the wave's staging area
-LR_D void trav_node_fetch(const TraversalStack &stack, const TravLane &tl, const TravState &tr, bool is_inner) {
+// (`node`: the packet this lane wants staged for itself; a lane that wants none names packet 0)
+LR_D void trav_node_fetch_of(const TraversalStack &stack, const TravLane &tl, uint32_t node) {
     typedef __attribute__((address_space(3))) void lds_void;
     typedef __attribute__((address_space(1))) const void global_void;
     // ---- cooperative packet fetch: 4 coalesced dwordx4 loads -> LDS (global_load_lds_dwordx4: no trip through the VGPRs)
     // -> 4 ds_read_b128 per lane.  Four consecutive lanes read one 64-byte packet: 16 lines per instruction, not 64
-    const auto want = (is_inner ? tr.cur : 0u) << 6u;
+    const auto want = node << 6u;
 #define LR_FETCH(j) { \
         const auto w = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(want), (j) * 0x55, 0xf, 0xf, true)) | tl.quarter; /* quad_perm:[j,j,j,j] */ \
         /* the instruction's immediate offset moves BOTH addresses: the four regions of the staging area are named by it (one M0 for all four loads), and the table base of load j is that much lower */ \
@@ -325,6 +326,7 @@ LR_D void trav_node_fetch(const TraversalStack &stack, const TravLane &tl, const
     LR_FETCH(0) LR_FETCH(1) LR_FETCH(2) LR_FETCH(3)
 #undef LR_FETCH
 }
+LR_D void trav_node_fetch(const TraversalStack &stack, const TravLane &tl, const TravState &tr, bool is_inner) { trav_node_fetch_of(stack, tl, is_inner ? tr.cur : 0u); }
 // every load of the iteration has landed: the packets are in the LDS
 LR_D void trav_fetch_wait() {
     __builtin_amdgcn_s_waitcnt(0);// vmcnt(0)
@@ -504,6 +506,8 @@ LR_D LeafTriangle trav_leaf_fetch(const TravLane &tl, uint32_t ref) {
 struct LeafRequest {
     LeafTriangle tri;
     bool at_leaf;// the lane stands at a leaf and its triangle is on its way
+    bool pair;   // PAIR (below): ... and the inner node on top of its stack is the packet it asked for
+    uint32_t pair_node;// (counting kernels: that node)
 };
 LR_D void trav_leaf_requests(const TravLane &tl, const TravState &tr, LeafRequest &rq) {
     // (the lanes that fetch no triangle never read one: their registers need a DEFINED value, not a particular one -- an empty asm "writes" them
@@ -642,9 +646,39 @@ LR_D void trav_leaf_step(const TraversalStack &stack, const TravLane &tl, TravSt
 // leaf (pool_trace: LR_POOL_EARLY_FETCH).
 // ALWAYS: the four packet loads go out even when no lane of the wave stands at an inner node (every lane then asks for packet 0, as the lanes
 // without a node always do): what pool_trace needs when rays may START between the two halves -- they start at the root, packet 0.
-template<bool COUNT, bool ALWAYS>
-LR_D bool trav_requests(const TraversalStack &stack, const TravLane &tl, const TravState &tr, LeafRequest &rq, bool leaves, TraceStats &stats) {
+//
+// PAIR (LR_POOL_LEAF_NODE_PAIR, megapool_kernel.h): A LEAF LANE TAKES ITS NEXT NODE IN THE SAME ITERATION.  A lane at a leaf used to ask for packet 0,
+// which nobody reads, and to sit out the node step.  If the entry on top of its stack lies in the LDS and names an inner node, it asks for THAT packet
+// in the slot it occupies anyway; trav_consume tests its triangle, pops -- the entry it asked for: nobody else writes a lane's stack -- and the lane
+// takes part in the node step with its own staged packet.  A shadow ray that found its occluder has dropped its stack and does not.  Which lane pairs
+// is a function of its `cur`, its `spb` and its own stack (trav_pair_candidate and the entry's sign): both halves see the same lanes, whatever runs
+// between them that leaves such lanes alone.  Every lane's triangle and slab tests stay in their order (t_max is the triangle test's before the
+// popped node's slab test); only their grouping into wave iterations changes.
+LR_D bool trav_pair_candidate(const TravLane &tl, uint32_t cur, uint32_t spb) {// at a leaf, with an entry, and that entry in the LDS part of the stack (sp <= kStackLds)
+    return static_cast<int>(cur) < static_cast<int>(kCurParked) && spb > tl.s_empty && spb <= tl.s_deep + 3u * kStackStride;
+}
+template<bool COUNT, bool ALWAYS, bool PAIR = false>
+LR_D bool trav_requests(const TraversalStack &stack, const TravLane &tl, const TravState &tr, uint32_t spb, LeafRequest &rq, bool leaves, TraceStats &stats) {
     const auto is_inner = static_cast<int>(tr.cur) >= 0;
+    if constexpr (PAIR) {
+        auto top = kInvalid;
+        if (trav_pair_candidate(tl, tr.cur, spb)) { top = spb_load(spb - kStackStride); }
+        rq.pair = static_cast<int>(top) >= 0;
+        if (COUNT) { rq.pair_node = top; }
+        // (the lane's own inner node, else the inner node on top of a leaf lane's stack, else packet 0: the largest of cur, top and 0 as integers -- a
+        // lane at an inner node is no candidate, a leaf and "nothing" are negative: one v_max3_i32)
+        const auto node = static_cast<uint32_t>(max(max(static_cast<int>(tr.cur), static_cast<int>(top)), 0));
+        // (the wave's vote is made on ONE compare, as every vote of the loop is: some lane stands at a node or a leaf -- a superset of the lanes
+        // at inner nodes and the paired ones; a node step that no lane takes part in costs a branch)
+        const auto any_node = ALWAYS || lr_any(tr.cur < kCurParked);
+        prio_chain();
+        if (any_node) { trav_node_fetch_of(stack, tl, node); }
+        if (leaves) { trav_leaf_requests(tl, tr, rq); }
+        LR_MARK(kProbeIssue);
+        (void)stats;
+        return any_node;
+    }
+    (void)spb;
     const auto any_inner = ALWAYS || lr_any(is_inner);
     prio_chain();
     if (any_inner) { trav_node_fetch(stack, tl, tr, is_inner); }
@@ -653,9 +687,10 @@ LR_D bool trav_requests(const TraversalStack &stack, const TravLane &tl, const T
     (void)stats;
     return any_inner;// the packet loads went out
 }
-// `any_inner`: some lane stands at an inner node NOW (its packet is among the requested ones); `deep`: some lane may reach the HBM overflow area of
-// the stack in this iteration (trav_iteration)
-template<bool COUNT, bool ALPHA>
+// `any_inner`: some lane stands at an inner node NOW (its packet is among the requested ones) or, PAIR, asked for the node on top of its stack;
+// `deep`: some lane may reach the HBM overflow area of the stack in this iteration (trav_iteration; a paired lane pops one entry out of the LDS and
+// pushes at most three: sp + 2, within the bound sp + 3 that the vote is made for)
+template<bool COUNT, bool ALPHA, bool PAIR = false>
 LR_D void trav_consume(const TraversalStack &stack, const TravLane &tl, TravState &tr, uint32_t &spb, f3 inv, LeafRequest &rq, bool any_inner, bool deep, TraceStats &stats) {
     const auto is_inner = static_cast<int>(tr.cur) >= 0;
     auto &tri = rq.tri;
@@ -663,18 +698,24 @@ LR_D void trav_consume(const TraversalStack &stack, const TravLane &tl, TravStat
     trav_fetch_wait();
     LR_MARK(kProbeVmWait);
     LR_PIN2(tri.a.x, tri.b.x, tri.c.x, tri.c.w);
+    [[maybe_unused]] auto joins = false;// PAIR: the lane has popped the node it asked for -- its packet is staged
     if (rq.at_leaf) {
         if (trav_leaf_test<COUNT, ALPHA>(tr, tr.cur, tri, stats)) { spb = tl.lds_base; }
+        [[maybe_unused]] const auto has = spb > tl.s_empty;// (the pop's own test: a shadow ray that found its occluder has dropped its stack)
         if (!ALPHA || !(tr.phase & kPhasePendingAlpha)) { tr.cur = trav_pop(stack, tl, spb, deep); }
         else { tr.cur |= kCurParkBit; }
+        if constexpr (PAIR) {
+            joins = rq.pair && (ALPHA ? static_cast<int>(tr.cur) >= 0 : has);// (ALPHA: a lane that parks a candidate keeps its leaf)
+            if (COUNT && joins && tr.cur != rq.pair_node) { stats.early_fetch_broken++; }
+        }
     }
     LR_MARK2(kProbeLeaf, tr.cur, spb);
-    if (any_inner) { trav_node_step<COUNT, true>(stack, tl, tr, spb, inv, is_inner, deep, stats); }
+    if (any_inner) { trav_node_step<COUNT, true>(stack, tl, tr, spb, inv, PAIR ? is_inner || joins : is_inner, deep, stats); }
 #if defined(LR_STALL_PROBE) && LR_STALL_PROBE < 2
     LR_MARK(kProbeChain, tr.cur, spb);// (level 1: everything of the walk behind the wait -- triangle test, slab tests, sort, pushes / pops)
 #endif
 }
-template<bool COUNT, bool ALPHA, bool FUSED = false>
+template<bool COUNT, bool ALPHA, bool FUSED = false, bool PAIR = false>
 LR_D void trav_iteration(const TraversalStack &stack, const TravLane &tl, TravState &tr, uint32_t &spb, f3 inv, TraceStats &stats) {
     const auto is_inner = static_cast<int>(tr.cur) >= 0;
     // one WAVE-LEVEL test per iteration decides whether any lane could touch the HBM overflow area of the stack in this iteration
@@ -683,8 +724,8 @@ LR_D void trav_iteration(const TraversalStack &stack, const TravLane &tl, TravSt
     const auto deep = lr_any(spb > tl.s_deep);
     if (FUSED) {// (LR_POOL_FUSED_FETCH: both gathers of the iteration requested up front, one wait)
         LeafRequest rq;
-        const auto any_inner = trav_requests<COUNT, false>(stack, tl, tr, rq, true, stats);
-        trav_consume<COUNT, ALPHA>(stack, tl, tr, spb, inv, rq, any_inner, deep, stats);
+        const auto any_inner = trav_requests<COUNT, false, PAIR>(stack, tl, tr, spb, rq, true, stats);
+        trav_consume<COUNT, ALPHA, PAIR>(stack, tl, tr, spb, inv, rq, any_inner, deep, stats);
         return;
     }
     if (lr_any(is_inner)) { trav_node_step<COUNT>(stack, tl, tr, spb, inv, is_inner, deep, stats); }

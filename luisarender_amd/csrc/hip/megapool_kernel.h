@@ -101,6 +101,18 @@ namespace lrd {
 // 246 VALU on both sides, <4096> still at 128 VGPRs without a spill.
 #define LR_POOL_EARLY_FETCH 1
 #endif
+#ifndef LR_POOL_LEAF_NODE_PAIR
+// LEAF / NODE PAIRING (fused flow only; dev_trace.h: PAIR).  A lane standing at a leaf spent a whole iteration on one triangle test while the wave's four
+// packet loads fetched packet 0 for it and the node step ran without it.  1 = if the entry on top of its stack (in the LDS) names an inner node, the
+// lane asks for that node's packet in the slot it occupies anyway, tests its triangle, pops, and takes part in the node step of the SAME iteration:
+// one memory round trip serves the triangle and the packet.  Same walk, same order of every lane's tests, same arithmetic: films and the ray, node
+// and triangle counters are bit-identical, only lane-iterations fall (tests/test_gpu_leaf_pair.py, against `make nopair`).  0 = the former code.
+// tools/bvh_sim.cpp predicts the share of triangle tests whose pop returns an inner node (C2 stand-in: 0.41 closest, 0.43 shadow).  Against the commit
+// before, same box, runs alternating (profiles/leaf_node_pair_ab.txt): lane-iterations per ray 21.11 -> 19.62 (- 7.1 %), C2 1195.5 -> 1221.2 Msamples/s
+// (+ 2.15 %, the runs of a side 0.06 - 0.18 % apart); <4096> still at 128 VGPRs without a spill.  The loop is issue-bound: the first form, + 33 instructions
+// per iteration (a per-lane select of the packet, a vote on a compound predicate), saved the same iterations and gained nothing -- 1194.6 against 1195.3.
+#define LR_POOL_LEAF_NODE_PAIR 1
+#endif
 #ifndef LR_POOL_EARLY_TAIL_PRIO
 #define LR_POOL_EARLY_TAIL_PRIO 3// the tail behind the early requests stays at the chain's priority (dev_trace.h: WAVE PRIORITIES); 0: it runs at the tests' priority (C2 1188 -> 1178)
 #endif
@@ -223,6 +235,7 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
     auto for_alpha = false;// (ALPHA: the wave leaves for the alpha tests of its parked candidates and comes straight back)
     constexpr bool FUSED = LR_POOL_FUSED_FETCH != 0 && (!ALPHA || LR_POOL_FUSED_ALPHA != 0);
     constexpr int EARLY = FUSED ? LR_POOL_EARLY_FETCH : 0;
+    constexpr bool PAIR = FUSED && LR_POOL_LEAF_NODE_PAIR != 0;
 #ifdef LR_STALL_PROBE
     if (COUNT) { probe_start(stats); }
 #endif
@@ -234,9 +247,13 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
     // but they are inputs of trav_consume, not of the requests.  The packet loads go out in EVERY iteration, also when no lane stands at an inner node
     // (trav_requests<.., ALWAYS>): a turnover may start rays in such a wave, too.  The counting kernels check every lane in every iteration
     // (early_fetch_broken -> lrhip_counters::probe[kProbeEarlyFetchBroken], which must stay 0).
+    // PAIR: a lane at a leaf whose stack top (in the LDS) names an inner node asks for that node's packet.  Its request reads its `cur`, its `spb` and
+    // that entry of its own stack, and the tail writes none of the three for a lane at a leaf: trav_consume pops the very entry.  An ended lane is no
+    // leaf lane and pairs with nothing; the ray a turnover starts for it stands at the root.  The counting kernels evaluate the rule once more behind
+    // the tail and compare -- which lanes pair, and with which node -- and trav_consume compares the node a paired lane pops with the one it asked for.
     LeafRequest rq;
     [[maybe_unused]] auto asked = tr.cur;// (counting kernels: what the lane's requests were made for)
-    if (EARLY != 0) { trav_requests<COUNT, true>(stack, tl, tr, rq, EARLY == 1, stats); }
+    if (EARLY != 0) { trav_requests<COUNT, true, PAIR>(stack, tl, tr, spb, rq, EARLY == 1, stats); }
     for (;;) {
         LR_MARK(kProbeTail, tr.cur);// (dev_trace.h, THE STALL PROBE: what the end of the previous iteration took)
         if (COUNT) {
@@ -253,15 +270,21 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
                 const auto same = tr.cur == asked || (asked == kInvalid && (tr.cur == 0u || tr.cur == kCurIdle));
                 const auto leaf = EARLY != 1 || rq.at_leaf == (static_cast<int>(tr.cur) < static_cast<int>(kCurParked));// (the triangle on its way is a leaf lane's)
                 stats.early_fetch_broken += same && leaf ? 0u : 1u;
+                if (PAIR) {
+                    auto pair = false;
+                    auto top = kInvalid;
+                    if (trav_pair_candidate(tl, tr.cur, spb)) { top = spb_load(spb - kStackStride), pair = static_cast<int>(top) >= 0; }
+                    stats.early_fetch_broken += pair == rq.pair && (!pair || top == rq.pair_node) ? 0u : 1u;
+                }
             }
             if (EARLY == 2) { trav_leaf_requests(tl, tr, rq); }
-            const auto any_inner = lr_any(static_cast<int>(tr.cur) >= 0), deep = lr_any(spb > tl.s_deep);// (from the lanes' state BEHIND the tail)
-            trav_consume<COUNT, ALPHA>(stack, tl, tr, spb, inv, rq, any_inner, deep, stats);
-            trav_requests<COUNT, true>(stack, tl, tr, rq, EARLY == 1, stats);
+            const auto any_inner = PAIR || lr_any(static_cast<int>(tr.cur) >= 0), deep = lr_any(spb > tl.s_deep);// (from the lanes' state BEHIND the tail; PAIR: a leaf lane may join the node step -- no vote: a wave in this loop all but always has a lane for it, and a node step without one is a skipped branch)
+            trav_consume<COUNT, ALPHA, PAIR>(stack, tl, tr, spb, inv, rq, any_inner, deep, stats);
+            trav_requests<COUNT, true, PAIR>(stack, tl, tr, spb, rq, EARLY == 1, stats);
             if (LR_POOL_EARLY_TAIL_PRIO == 0) { prio_tests(); }
             if (COUNT) { asked = tr.cur; }
         } else {
-            trav_iteration<COUNT, ALPHA, FUSED>(stack, tl, tr, spb, inv, stats);
+            trav_iteration<COUNT, ALPHA, FUSED, PAIR>(stack, tl, tr, spb, inv, stats);
         }
 #ifdef LR_TRACE_PROBE
         const auto probe_t1 = __builtin_readcyclecounter();

@@ -29,6 +29,9 @@ struct Stats {
     uint64_t pops{0}, stale_inner{0}, stale_leaf{0}, stale_chain[8]{};// stale_chain[k]: pops that skipped k stale entries in a row (k capped at 7)
     uint64_t depth_hist[64]{};// per ray: deepest stack
     uint64_t hits_hist[5]{};  // node visits by the number of children hit
+    // what a lane's pop returns behind a triangle test that does not end the ray: an inner node (the pool kernels pair the node's step with the
+    // triangle test, megapool_kernel.h: LR_POOL_LEAF_NODE_PAIR), a leaf, or nothing (the stack is empty)
+    uint64_t after_leaf[3]{};
 };
 static bool g_cull = false;
 static int g_partial_sort = 0;
@@ -98,6 +101,7 @@ static bool trace(const lr_accel &acc, V o, V d, float t_min, float t_max, bool 
                 if (any) { st.depth_hist[std::min(deepest, 63u)]++; return true; }
             }
             cur = pop();
+            st.after_leaf[cur == ~0u ? 2 : (cur & 0x80000000u) ? 1 : 0]++;
             continue;
         }
         auto &n = g_quantised ? g_qnodes[cur] : acc.nodes[cur];
@@ -221,6 +225,9 @@ int main(int argc, char **argv) {
     for (auto c : closest.stale_chain) { std::printf(" %.3f", per(c, closest.pops)); }
     std::printf("\nchildren hit per node visit 0..4 (closest | shadow):");
     for (int i = 0; i < 5; i++) { std::printf(" %.3f|%.3f", per(closest.hits_hist[i], closest.nodes), per(shadow.hits_hist[i], shadow.nodes)); }
+    std::printf("\nafter a triangle test the pop returns, share of triangle tests (closest | shadow; the rest of the shadow rays' tests found the occluder): inner node %.3f|%.3f  leaf %.3f|%.3f  nothing %.3f|%.3f",
+                per(closest.after_leaf[0], closest.tris), per(shadow.after_leaf[0], shadow.tris), per(closest.after_leaf[1], closest.tris), per(shadow.after_leaf[1], shadow.tris),
+                per(closest.after_leaf[2], closest.tris), per(shadow.after_leaf[2], shadow.tris));
     std::printf("\ndeepest stack per ray (closest | shadow), cumulative share of rays:");
     {
         uint64_t cc = 0, cs = 0;
