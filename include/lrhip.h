@@ -121,6 +121,40 @@ int lrhip_film_download(lrhip_ctx *ctx, float *rgba, int converted);
  * and cleared with the film by lrhip_film_clear; an AOV scene leaves the film itself untouched.  Synchronises.               */
 int lrhip_aov_download(lrhip_ctx *ctx, uint32_t component, float *out);
 
+/* The edge-avoiding a-trous wavelet filter (Dammertz et al. 2010; DESIGN §4.8 holds the definition) over per-pixel MEANS of colour c,
+ * albedo a, normal N and depth z.  With LRHIP_DENOISE_DEMODULATE, per channel a' = a where a > 1e-3 and 1 elsewhere (without it a' = 1),
+ * u_0 = c / a'; pass i = 0 .. iterations-1 has step s = 2^i and sigma_color * 2^-i, taps q = p + s (dx, dy), dx, dy in -2 .. 2, those
+ * outside the image skipped, weights k[dx+2] k[dy+2] exp(-d), k = (1/16, 1/4, 3/8, 1/4, 1/16),
+ *   d = |u(p)-u(q)|^2 / (sigma_color_i r(p))^2 + |N(p)-N(q)|^2 / sigma_normal^2 + (z(p)-z(q))^2 / (sigma_depth (|z(p)| + 1e-4))^2,
+ *   r(p) = mean of u(p)'s channels + 1e-4;  u_{i+1}(p) = sum w u_i(q) / sum w;  the output is u_iterations a'.
+ * Pixels that see only the environment (N = 0, z = 0, a = 0) mix among themselves.  The reference has no denoiser of its own (it leaves
+ * denoising to a LuisaCompute extension).  The working buffers (48 bytes per pixel) belong to the context and grow on demand. */
+typedef struct lrhip_denoise_params {
+    uint32_t width, height; /* lrhip_aov_denoise: 0 = the uploaded scene's; anything else must match it */
+    uint32_t iterations;    /* 1 .. LRHIP_DENOISE_MAX_ITERATIONS */
+    uint32_t flags;         /* LRHIP_DENOISE_* */
+    float sigma_color, sigma_normal, sigma_depth; /* each > 0 */
+} lrhip_denoise_params;
+#define LRHIP_DENOISE_DEMODULATE 1u
+#define LRHIP_DENOISE_MAX_ITERATIONS 8u
+#define LRHIP_DENOISE_DEFAULT_ITERATIONS 5u
+#define LRHIP_DENOISE_DEFAULT_SIGMA_COLOR 0.9f
+#define LRHIP_DENOISE_DEFAULT_SIGMA_NORMAL 0.35f
+#define LRHIP_DENOISE_DEFAULT_SIGMA_DEPTH 0.1f
+/* width = height = 0, the defaults above, LRHIP_DENOISE_DEMODULATE set */
+void lrhip_denoise_default_params(lrhip_denoise_params *params);
+/* Host arrays, interleaved as lrhip_aov_download gives them (color, albedo, normal, out: W x H x 3; depth: W x H), already divided by
+ * their sample counts.  Needs no uploaded scene: a MegaPath film is denoised with the guides of a short AOV run this way.  Synchronises. */
+int lrhip_denoise(lrhip_ctx *ctx, const lrhip_denoise_params *params, const float *color, const float *albedo, const float *normal,
+                  const float *depth, float *out);
+/* The same kernels on the device-resident sums of the uploaded AOV scene, without a trip through the host: `component` (LR_AOV_SAMPLE,
+ * LR_AOV_DIFFUSE or LR_AOV_SPECULAR) filtered under the scene's albedo, normal and depth, every sum times 1.0f / samples (the float
+ * product MegaPathRenderer.download_aov forms); out: W x H x 3.  LRHIP_ERROR_INVALID when one of the four components is not enabled.
+ * For whole frames: a context that rendered a tile shard holds the sums of its tiles only.  Synchronises. */
+int lrhip_aov_denoise(lrhip_ctx *ctx, const lrhip_denoise_params *params, uint32_t component, uint32_t samples, float *out);
+/* HIP-event time of the kernels (prepare, the passes, finish) of the last lrhip_denoise / lrhip_aov_denoise call, in ms */
+double lrhip_last_denoise_ms(lrhip_ctx *ctx);
+
 /* The path's only collective: sum-reduce of the per-rank films to rank `root` over RCCL / xGMI, in place on the film
  * this context accumulates into, in stream order behind the renders.  `nccl_comm` is the caller's ncclComm_t (one per process /
  * GPU, created by the caller: ncclCommInitRank); librccl.so is loaded on first use, so the library has no link-time dependency

@@ -52,6 +52,11 @@ int lrhost_scene_has_lighting(const lrhost_scene *scene);
  * noisy_count (samples per pixel, in place of the camera's spp; at least 8) and the dump strategy (LR_AOV_DUMP_*).  An error for
  * any other integrator. */
 int lrhost_scene_aov_settings(const lrhost_scene *scene, uint32_t *noisy_count, uint32_t *dump);
+/* The AOV integrator's denoise properties (ours; the reference ignores properties it does not know): denoise { false },
+ * denoise_iterations, denoise_sigma_color / _normal / _depth and denoise_demodulate, with lrhip.h's LRHIP_DENOISE_DEFAULT_* where the
+ * scene sets none.  sigmas = { color, normal, depth }.  `denoise { true }` needs the components sample, albedo, normal and depth: a
+ * scene that switches one of them off fails to load.  An error for any other integrator. */
+int lrhost_scene_aov_denoise(const lrhost_scene *scene, uint32_t *enabled, uint32_t *iterations, uint32_t *demodulate, float sigmas[3]);
 void lrhost_scene_destroy(lrhost_scene *scene);
 
 int lrhost_save_image(const char *path, const float *rgba, uint32_t width, uint32_t height);
@@ -61,7 +66,7 @@ int lrhost_save_image_channels(const char *path, const float *pixels, uint32_t w
 int lrhost_load_image(const char *path, float **rgba, uint32_t *width, uint32_t *height, uint32_t *channels);
 void lrhost_free(void *p);
 
-/* sizeof() of the lr_scene.h structs by name ("lr_scene", "lr_surface", ...), for FFI layout checks */
+/* sizeof() of the lr_scene.h structs by name ("lr_scene", "lr_surface", ...) and of lrhip.h's lrhip_denoise_params, for FFI layout checks */
 uint64_t lrhost_sizeof(const char *struct_name);
 
 void lrhost_set_log_level(int level); /* 0 silent, 1 warnings, 2 info */

@@ -127,7 +127,15 @@ class Scene(C.Structure):
                 ("media", C.POINTER(Medium)), ("medium_count", u32), ("pad_media", u32)]
 
 
-STRUCTS = {"lr_scene": Scene, "lr_vertex": Vertex, "lr_triangle": Triangle, "lr_alias_entry": AliasEntry,
+class DenoiseParams(C.Structure):
+    """lrhip_denoise_params (include/lrhip.h)"""
+    _fields_ = [("width", u32), ("height", u32), ("iterations", u32), ("flags", u32),
+                ("sigma_color", f32), ("sigma_normal", f32), ("sigma_depth", f32)]
+
+
+DENOISE_DEMODULATE = 1  # LRHIP_DENOISE_DEMODULATE
+
+STRUCTS = {"lrhip_denoise_params": DenoiseParams, "lr_scene": Scene, "lr_vertex": Vertex, "lr_triangle": Triangle, "lr_alias_entry": AliasEntry,
            "lr_mesh": Mesh, "lr_instance": Instance, "lr_texture": Texture, "lr_surface": Surface,
            "lr_light": Light, "lr_environment": Environment, "lr_camera": Camera, "lr_filter": Filter,
            "lr_film": Film, "lr_sampler": Sampler, "lr_integrator": Integrator, "lr_bvh4_node": Bvh4Node,
@@ -180,6 +188,7 @@ def host_lib() -> C.CDLL:
         lib.lrhost_save_image.argtypes = [C.c_char_p, C.c_void_p, u32, u32]
         lib.lrhost_save_image_channels.argtypes = [C.c_char_p, C.c_void_p, u32, u32, u32]
         lib.lrhost_scene_aov_settings.argtypes = [C.c_void_p, C.POINTER(u32), C.POINTER(u32)]
+        lib.lrhost_scene_aov_denoise.argtypes = [C.c_void_p, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(f32 * 3)]
         lib._lr_ready = True
     return lib
 
@@ -229,5 +238,11 @@ def hip_lib(path: str | None = None) -> C.CDLL:
         lib.lrhip_packed_texels.restype = C.c_uint64
         lib.lrhip_packed_texels.argtypes = [C.c_void_p]
         lib.lrhip_aov_download.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.lrhip_denoise_default_params.restype = None
+        lib.lrhip_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
+        lib.lrhip_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)] + [C.c_void_p] * 5
+        lib.lrhip_aov_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.lrhip_last_denoise_ms.restype = C.c_double
+        lib.lrhip_last_denoise_ms.argtypes = [C.c_void_p]
         lib._lr_ready = True
     return lib

@@ -106,6 +106,9 @@ void lrhip_destroy(lrhip_ctx *ctx) {
     release_scene(ctx);
     ctx->film_own.release(), ctx->converted.release(), ctx->partial.release();
     ctx->aov.release(), ctx->aov_partial.release();
+    ctx->denoise_guide.release(), ctx->denoise_colour[0].release(), ctx->denoise_colour[1].release(), ctx->denoise_inputs.release();
+    if (ctx->denoise_begin) { (void)hipEventDestroy(ctx->denoise_begin); }
+    if (ctx->denoise_end) { (void)hipEventDestroy(ctx->denoise_end); }
     ctx->spill.release(), ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->wf_counts.release(), ctx->wf_accum.release();
     ctx->pool.release(), ctx->counters.release(), ctx->work_counter.release(), ctx->scene_record.release();
     if (ctx->ev_begin) { (void)hipEventDestroy(ctx->ev_begin); }

@@ -7,6 +7,7 @@
 //   lrhip_render.hip     work items, fixed-point film, lrhip_render (one path per lane, pool, AOV)
 //   lrhip_wavefront.hip  the host loop of wavefront mode
 //   lrhip_comm.hip       the RCCL collectives
+//   lrhip_denoise.hip    the edge-avoiding wavelet filter over the AOV buffers (denoise_kernels.h)
 // Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
 #pragma once
 #include "../../../include/lrhip.h"
@@ -152,6 +153,11 @@ struct lrhip_ctx {
     uint32_t scheduler{0u};
     // the AOV integrator: planar sums [channel][pixel] of the enabled components (lrd::DScene::aov) and the chunks' partial planes
     lrh::DeviceBuffer aov, aov_partial;
+    // the denoiser (lrhip_denoise.hip): the guide { N, z } and two ping-pong colours, float4 per pixel each, and lrhip_denoise's copy of
+    // its host arrays; they grow on demand and outlive the scene
+    lrh::DeviceBuffer denoise_guide, denoise_colour[2], denoise_inputs;
+    hipEvent_t denoise_begin{nullptr}, denoise_end{nullptr};// around the kernels of the last call (lrhip_last_denoise_ms); made on first use
+    bool denoise_timed{false};
 };
 
 namespace lrh {

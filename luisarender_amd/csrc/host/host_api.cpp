@@ -117,6 +117,17 @@ int lrhost_scene_aov_settings(const lrhost_scene *scene, uint32_t *noisy_count, 
     });
 }
 
+int lrhost_scene_aov_denoise(const lrhost_scene *scene, uint32_t *enabled, uint32_t *iterations, uint32_t *demodulate, float sigmas[3]) {
+    return guarded([&] {
+        if (scene->data->integrator.kind != LR_INTEGRATOR_AOV) { throw lr::Error{"The scene's integrator is not AOV."}; }
+        const auto &p = scene->data->aov_denoise_params;
+        if (enabled) { *enabled = scene->data->aov_denoise ? 1u : 0u; }
+        if (iterations) { *iterations = p.iterations; }
+        if (demodulate) { *demodulate = (p.flags & LRHIP_DENOISE_DEMODULATE) != 0u ? 1u : 0u; }
+        if (sigmas) { sigmas[0] = p.sigma_color, sigmas[1] = p.sigma_normal, sigmas[2] = p.sigma_depth; }
+    });
+}
+
 void lrhost_scene_destroy(lrhost_scene *scene) { delete scene; }
 
 int lrhost_save_image(const char *path, const float *rgba, uint32_t width, uint32_t height) {
@@ -145,7 +156,7 @@ uint64_t lrhost_sizeof(const char *name) {
     LR_SIZEOF(lr_instance) LR_SIZEOF(lr_texture) LR_SIZEOF(lr_surface) LR_SIZEOF(lr_light) LR_SIZEOF(lr_environment)
     LR_SIZEOF(lr_camera) LR_SIZEOF(lr_filter) LR_SIZEOF(lr_film) LR_SIZEOF(lr_sampler) LR_SIZEOF(lr_integrator)
     LR_SIZEOF(lr_bvh4_node) LR_SIZEOF(lr_bvh_triangle) LR_SIZEOF(lr_accel) LR_SIZEOF(lr_light_handle)
-    LR_SIZEOF(lr_medium)
+    LR_SIZEOF(lr_medium) LR_SIZEOF(lrhip_denoise_params)
 #undef LR_SIZEOF
     return 0u;
 }

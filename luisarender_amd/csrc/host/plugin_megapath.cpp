@@ -46,6 +46,7 @@ struct HipApi {
     decltype(&lrhip_film_download) film_download{};
     decltype(&lrhip_last_error) last_error{};
     decltype(&lrhip_aov_download) aov_download{};// the AOV integrator
+    decltype(&lrhip_aov_denoise) aov_denoise{};  // ... with denoise { true }
     // multi-GPU: only looked up when the frame is sharded
     decltype(&lrhip_comm_init_all) comm_init_all{};
     decltype(&lrhip_comm_destroy) comm_destroy{};
@@ -68,6 +69,7 @@ struct HipApi {
         LR_SYM(film_download, "lrhip_film_download");
         LR_SYM(last_error, "lrhip_last_error");
         LR_SYM(aov_download, "lrhip_aov_download");
+        LR_SYM(aov_denoise, "lrhip_aov_denoise");
         LR_SYM(comm_init_all, "lrhip_comm_init_all");
         LR_SYM(comm_destroy, "lrhip_comm_destroy");
         LR_SYM(film_reduce_group, "lrhip_film_reduce_group");
@@ -80,6 +82,7 @@ struct HipApi {
 // one launch per sample (aov.cpp:410-412: one dispatch each), the auxiliary buffers cleared at the start of every shutter sample and
 // written as <parent>/<stem>_<component>_<n:05><ext> (<stem>_<component><ext> for the final dump) at the counts the dump strategy names,
 // each divided by float(1.0 / n) on the host (AuxiliaryBuffer::save, aov.cpp:173-189).  The camera's own file is never written.
+// denoise { true } (ours) adds <stem>_denoised_<n:05><ext> (<stem>_denoised<ext>) at the same counts: `sample` filtered on the device.
 template<typename Api, typename Data>
 void render_aov(Api &api, int device, Data &data, bool has_lighting) {
     lrhip_ctx *ctx = nullptr;
@@ -89,6 +92,10 @@ void render_aov(Api &api, int device, Data &data, bool has_lighting) {
     };
     if (api.aov_download == nullptr) {
         std::fprintf(stderr, "[error] liblrhip.so has no lrhip_aov_download\n");
+        std::abort();
+    }
+    if (data.aov_denoise && api.aov_denoise == nullptr) {
+        std::fprintf(stderr, "[error] liblrhip.so has no lrhip_aov_denoise\n");
         std::abort();
     }
     if (api.create(device, &ctx) != LRHIP_OK) { die("lrhip_create"); }
@@ -141,6 +148,14 @@ void render_aov(Api &api, int device, Data &data, bool has_lighting) {
                     std::snprintf(count, sizeof(count), "_%05u", n);
                     const auto name = stem + "_" + kNames[c] + (data.aov_dump == LR_AOV_DUMP_FINAL ? std::string{} : std::string{count}) + ext;
                     lr::save_image((parent / name).string(), buffer.data(), width, height, channels);
+                }
+                if (data.aov_denoise) {
+                    buffer.assign(static_cast<size_t>(width) * height * 3u, 0.f);
+                    if (api.aov_denoise(ctx, &data.aov_denoise_params, LR_AOV_SAMPLE, n, buffer.data()) != LRHIP_OK) { die("lrhip_aov_denoise"); }
+                    char count[16];
+                    std::snprintf(count, sizeof(count), "_%05u", n);
+                    const auto name = stem + "_denoised" + (data.aov_dump == LR_AOV_DUMP_FINAL ? std::string{} : std::string{count}) + ext;
+                    lr::save_image((parent / name).string(), buffer.data(), width, height, 3u);
                 }
             }
         }

@@ -1357,6 +1357,28 @@ public:
                 if (dump != "power2") { log_warning("Unknown dump strategy '" + dump + "'. Fallback to power2 strategy. [" + integrator->location() + "]"); }
                 _out.aov_dump = LR_AOV_DUMP_POWER2;
             }
+            // the edge-avoiding wavelet filter over the finished buffers: properties of ours, which the reference ignores
+            _out.aov_denoise = integrator->bool_or("denoise", false);
+            auto &dn = _out.aov_denoise_params;
+            dn.iterations = integrator->uint_or("denoise_iterations", LRHIP_DENOISE_DEFAULT_ITERATIONS);
+            dn.sigma_color = integrator->float_or("denoise_sigma_color", LRHIP_DENOISE_DEFAULT_SIGMA_COLOR);
+            dn.sigma_normal = integrator->float_or("denoise_sigma_normal", LRHIP_DENOISE_DEFAULT_SIGMA_NORMAL);
+            dn.sigma_depth = integrator->float_or("denoise_sigma_depth", LRHIP_DENOISE_DEFAULT_SIGMA_DEPTH);
+            dn.flags = integrator->bool_or("denoise_demodulate", true) ? LRHIP_DENOISE_DEMODULATE : 0u;
+            if (_out.aov_denoise) {
+                for (auto k : {LR_AOV_SAMPLE, LR_AOV_ALBEDO, LR_AOV_NORMAL, LR_AOV_DEPTH}) {
+                    if ((flags & LR_AOV_BIT(k)) == 0u) {
+                        throw Error{std::string{"denoise { true } needs the AOV component '"} + kNames[k] + "', which `components` leaves out. [" +
+                                    integrator->location() + "]"};
+                    }
+                }
+                if (dn.iterations < 1u || dn.iterations > LRHIP_DENOISE_MAX_ITERATIONS) {
+                    throw Error{"denoise_iterations must be 1 .. " + std::to_string(LRHIP_DENOISE_MAX_ITERATIONS) + ". [" + integrator->location() + "]"};
+                }
+                if (!(dn.sigma_color > 0.f) || !(dn.sigma_normal > 0.f) || !(dn.sigma_depth > 0.f)) {
+                    throw Error{"denoise_sigma_color / _normal / _depth must be positive. [" + integrator->location() + "]"};
+                }
+            }
         } else {
             throw Error{"Integrator '" + integrator->impl_type() + "' is out of scope: this framework implements the MegaPath hot "
                         "path and its sibling megakernels Direct / Normal / MegaVPTNaive (SURVEY §2 row 21, §8 f3-f4)."};

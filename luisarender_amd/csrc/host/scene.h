@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../../include/lr_scene.h"
+#include "../../../include/lrhip.h"
 #include "sdl.h"
 #include "lr_math.h"
 
@@ -79,6 +80,10 @@ struct SceneData {
     std::string integrator_impl;
     uint32_t aov_noisy_count{8u};          // the AOV integrator (aov.cpp:53): samples per pixel, in place of the camera's
     uint32_t aov_dump{LR_AOV_DUMP_POWER2}; // LR_AOV_DUMP_*
+    // the AOV integrator's denoise properties (ours: lrhost.h lrhost_scene_aov_denoise); width and height stay 0 = the camera's
+    bool aov_denoise{false};
+    lrhip_denoise_params aov_denoise_params{0u, 0u, LRHIP_DENOISE_DEFAULT_ITERATIONS, LRHIP_DENOISE_DEMODULATE, LRHIP_DENOISE_DEFAULT_SIGMA_COLOR,
+                                            LRHIP_DENOISE_DEFAULT_SIGMA_NORMAL, LRHIP_DENOISE_DEFAULT_SIGMA_DEPTH};
     bool any_non_opaque{false};
     // animation (src/transforms/lerp.cpp, Geometry::update geometry.cpp:194-216, Pipeline::update pipeline.cpp:101-113)
     std::vector<XformNode> xforms;

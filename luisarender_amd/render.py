@@ -125,6 +125,43 @@ class MegaPathRenderer:
             out *= np.float32(1.0 / max(self._aov_samples, 1))
         return out
 
+    def _denoise_params(self, width: int, height: int, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None,
+                        demodulate=None) -> _ffi.DenoiseParams:
+        p = _ffi.DenoiseParams()
+        self._lib.lrhip_denoise_default_params(C.byref(p))
+        p.width, p.height = width, height
+        for name, value in (("iterations", iterations), ("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
+            if value is not None:
+                setattr(p, name, value)
+        if demodulate is not None:
+            p.flags = _ffi.DENOISE_DEMODULATE if demodulate else 0
+        return p
+
+    def denoise(self, color: np.ndarray, albedo: np.ndarray, normal: np.ndarray, depth: np.ndarray, **params) -> np.ndarray:
+        """lrhip_denoise: the edge-avoiding wavelet filter over per-pixel means -- color, albedo, normal [H, W, 3] and depth
+        [H, W] or [H, W, 1], as download_aov gives them -- on the device; needs no uploaded scene.  params: iterations (1 .. 8), sigma_color,
+        sigma_normal, sigma_depth, demodulate; lrhip.h's defaults otherwise.  Returns [H, W, 3]."""
+        color, albedo, normal, depth = (np.ascontiguousarray(a, dtype=np.float32) for a in (color, albedo, normal, depth))
+        h, w = color.shape[:2]
+        if color.shape != (h, w, 3) or albedo.shape != color.shape or normal.shape != color.shape or depth.size != h * w:
+            raise ValueError(f"denoise: shapes {color.shape}, {albedo.shape}, {normal.shape}, {depth.shape}")
+        out = np.empty((h, w, 3), np.float32)
+        self._check(self._lib.lrhip_denoise(self._ctx, C.byref(self._denoise_params(w, h, **params)), color.ctypes.data, albedo.ctypes.data,
+                                            normal.ctypes.data, depth.ctypes.data, out.ctypes.data))
+        return out
+
+    def denoise_aov(self, component: str = "sample", **params) -> np.ndarray:
+        """lrhip_aov_denoise: the same filter over the buffers on the device -- `component` (sample, diffuse or specular) under the scene's
+        albedo, normal and depth, each divided by the samples per pixel rendered since the last upload or clear().  Whole frames only.
+        Equals denoise(download_aov(component), download_aov("albedo"), ...) bit for bit."""
+        out = np.empty((self.height, self.width, 3), np.float32)
+        self._check(self._lib.lrhip_aov_denoise(self._ctx, C.byref(self._denoise_params(0, 0, **params)), AOV_COMPONENTS.index(component),
+                                                self._aov_samples, out.ctypes.data))
+        return out
+
+    def last_denoise_ms(self) -> float:
+        return float(self._lib.lrhip_last_denoise_ms(self._ctx))
+
     # ---- the one collective of the multi-GPU path (SURVEY 8e), through the C ABI
     def comm_unique_id(self) -> bytes:
         buf = (C.c_ubyte * 128)()

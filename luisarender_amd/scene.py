@@ -108,15 +108,30 @@ class Scene:
     def has_lighting(self) -> bool:
         return bool(self._lib.lrhost_scene_has_lighting(self._handle))
 
+    def aov_denoise(self) -> dict:
+        """lrhost_scene_aov_denoise: the AOV integrator's denoise properties -- "enabled" (denoise { false }) and, with lrhip.h's
+        defaults where the scene sets none, MegaPathRenderer.denoise_aov's keywords iterations, sigma_color, sigma_normal, sigma_depth and
+        demodulate.  HostError for any other integrator."""
+        enabled, iterations, demodulate, sigmas = C.c_uint32(), C.c_uint32(), C.c_uint32(), (C.c_float * 3)()
+        if self._lib.lrhost_scene_aov_denoise(self._handle, C.byref(enabled), C.byref(iterations), C.byref(demodulate), C.byref(sigmas)) != 0:
+            raise HostError(self._lib.lrhost_last_error().decode())
+        return {"enabled": bool(enabled.value), "iterations": iterations.value, "sigma_color": float(sigmas[0]),
+                "sigma_normal": float(sigmas[1]), "sigma_depth": float(sigmas[2]), "demodulate": bool(demodulate.value)}
+
     def aov_settings(self) -> dict:
         """The AOV integrator's settings (src/integrators/aov.cpp:48-87): the enabled components (AOV_COMPONENTS order), noisy_count (samples
-        per pixel, in place of the camera's spp), the dump strategy and the path depth.  HostError for any other integrator."""
+        per pixel, in place of the camera's spp), the dump strategy and the path depth.  A scene with denoise { true } has one more key,
+        "denoise": aov_denoise() without "enabled", i.e. the keywords of MegaPathRenderer.denoise_aov.  HostError for any other integrator."""
         n, dump = C.c_uint32(), C.c_uint32()
         if self._lib.lrhost_scene_aov_settings(self._handle, C.byref(n), C.byref(dump)) != 0:
             raise HostError(self._lib.lrhost_last_error().decode())
         integrator = self.view().integrator
-        return {"components": [c for k, c in enumerate(AOV_COMPONENTS) if (integrator.flags >> k) & 1], "noisy_count": n.value,
-                "dump": AOV_DUMPS[dump.value], "depth": int(integrator.max_depth)}
+        settings = {"components": [c for k, c in enumerate(AOV_COMPONENTS) if (integrator.flags >> k) & 1], "noisy_count": n.value,
+                    "dump": AOV_DUMPS[dump.value], "depth": int(integrator.max_depth)}
+        denoise = self.aov_denoise()
+        if denoise.pop("enabled"):
+            settings["denoise"] = denoise
+        return settings
 
     def resolution(self, camera: int = 0) -> tuple[int, int]:
         v = self.view(camera)
