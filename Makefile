@@ -31,8 +31,8 @@ HOST_HDR := $(wildcard $(HOSTDIR)/*.h) $(wildcard include/*.h)
 HIP_SRC := $(wildcard $(HIPDIR)/lrhip_*.hip)
 HIP_HDR := $(wildcard $(HIPDIR)/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly nopair
-all: host oracle hip cli ieee shallow noearly nopair
+.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly nopair noride
+all: host oracle hip cli ieee shallow noearly nopair noride
 
 # oracle/_ref: the reference's OWN sources compiled in place against the scalar LuisaCompute stand-in of oracle/ref_shim
 # (test infrastructure: pins oracle/ to the reference; needs /root/reference, so only where the reference tree exists)
@@ -145,6 +145,15 @@ $(LIBDIR)/variants/liblrhip_noearly.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hi
 nopair: $(LIBDIR)/variants/liblrhip_nopair.so
 $(LIBDIR)/variants/liblrhip_nopair.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
 	$(MAKE) --no-print-directory hip-variant NAME=nopair DEFS='-DLR_POOL_LEAF_NODE_PAIR=0' VARIANT_MASKS='4096 4097 4100 4101' HEAVY_MASKS=
+
+# Pool kernels once more WITHOUT the shadow ride (megapool_kernel.h: LR_POOL_SHADOW_RIDE): a path whose last vertex has a light sample stays open for
+# a job that holds that shadow ray alone.  The lean kernels, the environment set, Disney with an environment, the run-time generic sampler, PaddedSobol
+# and the 8-bit-texel Disney set, each with its counting twin.  TEST INFRASTRUCTURE: the ride changes which batch starts which sample and when a
+# finished sample joins the film, nothing else, so the shipped library's frames and its path / ray / node / triangle / shaded-vertex counters must equal
+# this library's (tests/test_gpu_shadow_ride.py).
+noride: $(LIBDIR)/variants/liblrhip_noride.so
+$(LIBDIR)/variants/liblrhip_noride.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
+	$(MAKE) --no-print-directory hip-variant NAME=noride DEFS='-DLR_POOL_SHADOW_RIDE=0' VARIANT_MASKS='4096 4097 4098 4099 4100 4101 4102 4103 4116 4117 20482 20483 12308 12309' HEAVY_MASKS=
 
 cli: $(BINDIR)/luisa-render-cli
 $(BINDIR)/luisa-render-cli: $(HOSTDIR)/cli.cpp $(HOSTDIR)/plugin_megapath.cpp $(LIBDIR)/liblrhost.so $(HOST_HDR)

@@ -95,10 +95,10 @@ bool wants_pool(const lrhip_ctx *ctx) {
     return ctx->scheduler == 2u || (ctx->scheduler == 0u && ctx->update_counts[1] >= pool_auto_triangles(ctx->scene.max_depth,
         ctx->scene.sampler_spp));
 }
-// path state of the pool kernels: two contexts per thread, 4 (Independent sampler) | 5 float4 each, [context][quad][thread]
-// (megapool_kernel.h); sized for 5
+// path state of the pool kernels: two contexts per thread, 4 (Independent sampler) | 5 float4 each and one more for the ids of a path
+// whose last shadow ray rides with the next one (LR_POOL_SHADOW_RIDE), [context][quad][thread] (megapool_kernel.h); sized for 6
 int ensure_pool(lrhip_ctx *ctx, uint32_t resident_blocks) {
-    return ensure(ctx->pool, static_cast<size_t>(resident_blocks) * lrd::kWavesPerBlock * lrd::kPoolSlots * lrd::pool_quads<true>()
+    return ensure(ctx->pool, static_cast<size_t>(resident_blocks) * lrd::kWavesPerBlock * lrd::kPoolSlots * lrd::kPoolRecordQuadsMax
         * sizeof(float4));
 }
 

@@ -122,14 +122,35 @@ namespace lrd {
 #ifndef LR_POOL_RAY_INIT
 #define LR_POOL_RAY_INIT if (!mine)
 #endif
+#ifndef LR_POOL_SHADOW_RIDE
+// SHADOW RIDE (every pool kernel but the wavefront passes).  A path's last vertex spawns no closest-hit ray, and where it has a light sample the context
+// used to stay open for one more job that held the shadow ray alone: traced, turned over and counted towards LR_POOL_SHADE_LANES like any other, it then
+// took a lane of a shading batch for `Li += nee` and one film add -- about 0.7 such jobs per path on C2 beside 3.05 shaded vertices.  1 = such a context
+// asks for a sample like an empty one; if it gets one, the finished path's Li and nee STAY in their words of the record (a fresh path's are zero: the
+// six words are free during its first job), the finished path's pixel, work item and pixel in tile go into one more quad, bit 22 of the packed depth
+// word marks the record, and the job is {the old path's shadow ray, the new path's camera ray}: an ordinary mid-path job to the traversal loop.  Where
+// that job is shaded the old path is completed first -- the same `Li += nee`, the same completion code (LR_POOL_FILM_ADD below) -- and the new path's first
+// vertex follows with Li = nee = 0.  A context that gets no sample (the launch has none left) goes on with the shadow-only job.  Every ray, random
+// number and float operation of every path is unchanged; which batch hands a sample number to which context and when an integer joins the film are
+// not: films and the path / ray / node / triangle / shaded-vertex counters are bit-identical, only batches fall (tests/test_gpu_shadow_ride.py,
+// against `make noride`).  0 = the former code.  Against the commit before, same box, three runs a side alternating (profiles/shadow_ride_ab.txt): C2 1221.1 ->
+// 1288.2 Msamples/s (+ 5.5 %, the runs of a side 0.14 - 0.18 % apart), C3 1209 -> 1277, C4 1329 -> 1580, C2 under PaddedSobol 1118 -> 1202; lanes.shade 0.646 ->
+// 0.835, batch slots per sample 4.72 -> 3.65, VALU wave instructions per sample 568 -> 536; <4096> still at 128 VGPRs without a spill, the traversal loop's
+// instructions unchanged; the wavefront passes' code objects byte-identical (their contexts keep the shadow-only job: RIDE below).
+#define LR_POOL_SHADOW_RIDE 1
+#endif
 constexpr uint32_t kPoolSlots = 128u;// paths per wave: two contexts per lane
 
 // ---- path state of one context in global memory: kPoolQuads float4 at [context][quad][thread]
-//   0  nee.xyz | pdf_bsdf        1  beta.xyz | depth (16) | pixel in tile (6) << 16
+//   0  nee.xyz | pdf_bsdf        1  beta.xyz | depth (16) | pixel in tile (6) << 16 | pending (1) << 22
 //   2  Li.xyz | sampler word 0   3  pixel index (frame) | work item of the path | sampler words 1-2
 //   4  sampler word 3 (generic sampler only)
+//   LR_POOL_SHADOW_RIDE, behind the last of these (index 4, or 5 under the run-time generic sampler): pixel index | work item | pixel in tile of the
+//   path that ended where this one began.  While `pending` is set, nee.xyz and Li.xyz are THAT path's; everything else is the new path's.
 template<bool GENERIC>
 constexpr uint32_t pool_quads() { return GENERIC ? 5u : 4u; }
+constexpr uint32_t kPoolRecordQuadsMax = pool_quads<true>() + 1u;// (what the host sizes a context's record for: lrhip_render.hip, ensure_pool)
+constexpr uint32_t kPoolPending = 1u << 22u;
 
 // ---- one of a lane's two path contexts as the traversal loop sees it (registers)
 enum : uint32_t {
@@ -375,6 +396,28 @@ template<bool ENV>
     return sample_one_light<ENV>(*scene, it, u0, f2{u1, u2});
 }
 
+// A path is complete: film.accumulate (integrator.cpp:74) of its radiance L; OF_ITEM the work item it was started in, TILE_PIXEL its pixel in that
+// item's tile.  The one piece of source through which a sample joins the film: the shading block of megapool_kernel expands it where a path ends
+// and (LR_POOL_SHADOW_RIDE) where the job that carried a finished path's last shadow ray is shaded.  (A macro, not a lambda: through a lambda the
+// wavefront passes, which expand it once, came out with their instructions in another order; their code objects are to stay what they were.)
+#define LR_POOL_FILM_ADD(L, PIXEL, OF_ITEM, TILE_PIXEL)                                                                                          \
+    do {                                                                                                                                         \
+        const auto rgb = (L) * scene.shutter_weight;                                                                                             \
+        if (CONT || (OF_ITEM) != item) {/* (its wave has left the path's work item: the frame's sums directly) */                                \
+            wf_film_accumulate(scene, args.film, (PIXEL), rgb, scene.film_clamp);                                                                \
+        } else if (!(any_nan(rgb) || any_inf(rgb))) {/* ColorFilmInstance::_accumulate (color.cpp:107-130, effective_spp = 1) into the tile */   \
+            const auto threshold = scene.film_clamp * fmaxf(1.f, 1.f);                                                                           \
+            const auto strength = fmaxf(fmaxf(fmaxf(fabsf(rgb.x), fabsf(rgb.y)), fabsf(rgb.z)), 0.f);                                            \
+            const auto c = rgb * (threshold / fmaxf(strength, threshold));                                                                       \
+            const auto px_sums = film_tile + (TILE_PIXEL) * 3u;                                                                                  \
+            if (c.x != 0.f) { atomicAdd(px_sums + 0, radiance_to_fixed(c.x, scene.wf.accum_scale)); }                                            \
+            if (c.y != 0.f) { atomicAdd(px_sums + 1, radiance_to_fixed(c.y, scene.wf.accum_scale)); }                                            \
+            if (c.z != 0.f) { atomicAdd(px_sums + 2, radiance_to_fixed(c.z, scene.wf.accum_scale)); }                                            \
+        } else {/* rejected: the flush counts every sample of the item */                                                                        \
+            atomicAdd(&args.film[(PIXEL)].w, -1.f);                                                                                              \
+        }                                                                                                                                        \
+    } while (false)
+
 template<uint32_t F>
 __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(DScenePtr scene_ptr, RenderArgs args) {
     const DScene &scene = *(const DScene *)scene_ptr;
@@ -399,6 +442,9 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
 #endif
     static_assert(PADDED == ((F & kFeatPadded) != 0u) || (F & kFeatPadded) == 0u, "a kFeatPadded kernel: generic sampler, LR_ONLY_SAMPLER = PaddedSobol");
     constexpr uint32_t QUADS = PADDED ? 4u : pool_quads<PCG>();
+    constexpr bool RIDE = LR_POOL_SHADOW_RIDE != 0 && !WF;// (the wavefront passes keep the shadow-only job)
+    constexpr uint32_t RECORD = QUADS + (RIDE ? 1u : 0u);  // quads of a context's record: quad QUADS holds the ids of a path whose last shadow ray rides along
+    static_assert(RECORD <= kPoolRecordQuadsMax, "ensure_pool sizes the records");
     __shared__ uint32_t s_stack[kStackLds * kBlockThreads];
     __shared__ float4 s_stage[kWavesPerBlock * kStageWave];// 4 KiB of node packets per wave
 #if LR_POOL_PARK_ON_STACK == 0
@@ -422,8 +468,8 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
     const auto wave_in_block = __builtin_amdgcn_readfirstlane(tid >> 6u);
     TraversalStack stack{s_stack + tid, args.spill + gtid, args.total_threads, s_stage + wave_in_block * kStageWave};
     const auto film_tile = s_film + (CONT ? 0u : wave_in_block * 192u);
-    // path state of this thread's two contexts: quad q of context c at args.pool[(c * QUADS + q) * total_threads + gtid]
-    const auto state_of = [&](uint32_t side, uint32_t quad) { return args.pool + static_cast<size_t>(side * QUADS + quad) * args.total_threads + gtid; };
+    // path state of this thread's two contexts: quad q of context c at args.pool[(c * RECORD + q) * total_threads + gtid]
+    const auto state_of = [&](uint32_t side, uint32_t quad) { return args.pool + static_cast<size_t>(side * RECORD + quad) * args.total_threads + gtid; };
     // (as 16-byte quads.  Word by word -- no register tuples for the allocator to place -- was tried: 46 -> 60 spilled VGPRs)
     const auto state_load = [&](uint32_t side, uint32_t quad) { return *state_of(side, quad); };
     const auto state_store = [&](uint32_t side, uint32_t quad, float4 v) { *state_of(side, quad) = v; };
@@ -600,7 +646,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                 nee = mk3(q0.x, q0.y, q0.z), pdf_bsdf = q0.w;
                 beta = mk3(q1.x, q1.y, q1.z);
                 const auto packed = __float_as_uint(q1.w);
-                dp = packed & 0x3fffffu;
+                dp = packed & (RIDE ? 0x7fffffu : 0x3fffffu);
                 Li = mk3(q2.x, q2.y, q2.z);
                 word0 = __float_as_uint(q2.w);
                 if (!LEAN_STATE) { load_ids(); }
@@ -620,6 +666,12 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
             if (path_open) {
                 if (traced_shadow) {// direct lighting of the bounce that spawned the shadow ray, mega_path.cpp:124-130
                     if (!occluded) { Li += nee; }
+                }
+                if (RIDE && (dp & kPoolPending) != 0u) {// that shadow ray was the last one of the path before: Li is its radiance, the ids wait in the extra quad
+                    const auto ids = state_load(side, QUADS);
+                    LR_POOL_FILM_ADD(Li, __float_as_uint(ids.x), __float_as_uint(ids.y), __float_as_uint(ids.z));
+                    Li = mk3(0.f), nee = mk3(0.f);// (this context's path: its camera ray is the segment the job traced)
+                    dp &= ~kPoolPending;
                 }
                 if (traced_closest) {// one iteration of the reference's depth loop, mega_path.cpp:63-154
                     if (COUNT) { local.shade_busy++; }
@@ -810,20 +862,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
             }
             if (path_open && !want_shadow && !want_closest) {// path complete: film.accumulate (integrator.cpp:74)
                 if (LEAN_STATE) { load_ids(); }
-                const auto rgb = Li * scene.shutter_weight;
-                if (CONT || path_item != item) {// (its wave has left the path's work item: the frame's sums directly)
-                    wf_film_accumulate(scene, args.film, pixel_index, rgb, scene.film_clamp);
-                } else if (!(any_nan(rgb) || any_inf(rgb))) {// ColorFilmInstance::_accumulate (color.cpp:107-130, effective_spp = 1) into the tile
-                    const auto threshold = scene.film_clamp * fmaxf(1.f, 1.f);
-                    const auto strength = fmaxf(fmaxf(fmaxf(fabsf(rgb.x), fabsf(rgb.y)), fabsf(rgb.z)), 0.f);
-                    const auto c = rgb * (threshold / fmaxf(strength, threshold));
-                    const auto px_sums = film_tile + (dp >> 16u) * 3u;
-                    if (c.x != 0.f) { atomicAdd(px_sums + 0, radiance_to_fixed(c.x, scene.wf.accum_scale)); }
-                    if (c.y != 0.f) { atomicAdd(px_sums + 1, radiance_to_fixed(c.y, scene.wf.accum_scale)); }
-                    if (c.z != 0.f) { atomicAdd(px_sums + 2, radiance_to_fixed(c.z, scene.wf.accum_scale)); }
-                } else {// rejected: the flush counts every sample of the item
-                    atomicAdd(&args.film[pixel_index].w, -1.f);
-                }
+                LR_POOL_FILM_ADD(Li, pixel_index, path_item, dp >> 16u);
                 path_open = false;
             }
             // ==== (A') path regeneration: contexts without a path take the next samples of the item's queue, in lane order
@@ -834,7 +873,10 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
             // The loop below only HANDS OUT sample numbers (it is a loop because the wave may walk into its next work item half way through
             // the batch, and because a pixel beyond the frame's edge has no samples: such a lane asks again); the work of starting a path
             // follows it once.  (With the camera code inside the loop the register allocator took the whole shading block for a cold one.)
-            auto need = mine && !path_open;// (a context without a path: it takes the next sample, if the launch has one left)
+            // LR_POOL_SHADOW_RIDE: a path that only waits for its last shadow ray asks like a context without one; if it gets a sample the shadow ray
+            // rides with that path's camera ray, and if it gets none the shadow-only job follows as it used to
+            const auto final_shadow = RIDE && path_open && want_shadow && !want_closest;
+            auto need = mine && (!path_open || final_shadow);// (a context without a path: it takes the next sample, if the launch has one left)
             auto got = false;
             auto new_k = 0u, new_item = kInvalid, new_px = 0u, new_py = 0u, new_s = 0u;
             for (;;) {
@@ -879,6 +921,10 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                     sampler.restore(scene, words);
                     path_open = true;
                 } else {// MegakernelPathTracingInstance::Li prologue, mega_path.cpp:52-62
+                    if (final_shadow) {// the ids of the path that ends leave for the extra quad here: nothing of it is alive across the camera code
+                        if (LEAN_STATE) { load_ids(); }
+                        state_store(side, QUADS, make_float4(__uint_as_float(pixel_index), __uint_as_float(path_item), __uint_as_float(dp >> 16u), 0.f));
+                    }
                     pixel_index = new_py * scene.camera.width + new_px;
                     path_item = new_item;
                     // (MEASURED, NOT KEPT, round 6: this start of a path -- seed, filter tables, camera ray -- as one real call like the light sample: camera class
@@ -889,10 +935,10 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                     float weight;
                     camera_ray(scene, scene.filter, new_px, new_py, u_filter, u_lens, ray, weight);
                     beta = mk3(weight);
-                    Li = mk3(0.f), nee = mk3(0.f);
+                    if (!final_shadow) { Li = mk3(0.f), nee = mk3(0.f); }// (else: the old path's, in their words of the record until its shadow ray is traced)
                     pdf_bsdf = 1e16f;
-                    dp = (new_k & 63u) << 16u;
-                    path_open = true, want_shadow = false, want_closest = true;
+                    dp = ((new_k & 63u) << 16u) | (final_shadow ? kPoolPending : 0u);
+                    path_open = true, want_shadow = final_shadow, want_closest = true;
                     if (COUNT) { local.paths++; }
                 }
             }
@@ -1047,5 +1093,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
         reduce(local.shade_regen_cycles, &args.counters->shade_regen_cycles);
     }
 }
+
+#undef LR_POOL_FILM_ADD
 
 }// namespace lrd
