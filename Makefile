@@ -100,9 +100,13 @@ $(OBJDIR)/heavy_%.o: $(HIPDIR)/heavy_variant.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(CALL_SAFE_FLAGS) $(HEAVY_DEFS) -DLR_HVARIANT=$* -c -o $@ $(HIPDIR)/heavy_variant.hip
 HIP_OBJ := $(patsubst $(HIPDIR)/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
+# lrhip_raycast.o holds kernels of its own (csrc/hip/raycast_kernel.h: ray queries); the one with the alpha test calls the texture code, so it takes
+# the variants' safe flag.  RAYCAST_DEFS: its A/B builds (make hip-variant NAME=r64 RAYCAST_DEFS=-DLR_RAYCAST_REFILL=64 VARIANT_MASKS=0 HEAVY_MASKS=)
+RAYCAST_DEFS ?=
+lrhip_raycast_FLAGS = $(CALL_SAFE_FLAGS) $(RAYCAST_DEFS)
 $(HIP_OBJ): $(OBJDIR)/%.o: $(HIPDIR)/%.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+	$(HIPCC) $(HIPFLAGS) $($*_FLAGS) -c -o $@ $<
 $(LIBDIR)/liblrhip.so: $(HIP_OBJ) $(VARIANT_OBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -o $@ $^
 
@@ -111,7 +115,7 @@ $(LIBDIR)/liblrhip.so: $(HIP_OBJ) $(VARIANT_OBJ)
 VOBJDIR := $(LIBDIR)/variants/obj_$(NAME)
 hip-variant:
 	@mkdir -p $(VOBJDIR)
-	$(MAKE) --no-print-directory OBJDIR=$(VOBJDIR) HIPFLAGS='$(HIPFLAGS) $(DEFS)' VARIANT_MASKS='$(VARIANT_MASKS)' HEAVY_MASKS='$(HEAVY_MASKS)' \
+	$(MAKE) --no-print-directory OBJDIR=$(VOBJDIR) HIPFLAGS='$(HIPFLAGS) $(DEFS)' VARIANT_MASKS='$(VARIANT_MASKS)' HEAVY_MASKS='$(HEAVY_MASKS)' RAYCAST_DEFS='$(RAYCAST_DEFS)' \
 	    LIBDIR_OUT=$(LIBDIR)/variants/liblrhip_$(NAME).so variant-lib
 variant-lib: $(HIP_OBJ) $(VARIANT_OBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -o $(LIBDIR_OUT) $^

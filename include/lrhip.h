@@ -16,6 +16,7 @@
  *                                  Li() + film accumulate                 src/integrators/mega_path.cpp:49-156
  *   lrhip_film_download            ColorFilmInstance::download            src/films/color.cpp:99-105
  *   lrhip_film_reduce              (no reference equivalent: the one collective of the multi-GPU path)
+ *   lrhip_trace_rays               (no reference entry point: Geometry::trace_closest / trace_any for the caller's rays)
  *   lrhip_get_counters             (no reference equivalent; roofline accounting)
  *
  * Conventions: 0 = OK, negative = error (text via lrhip_last_error, thread-local); nothing
@@ -154,6 +155,46 @@ int lrhip_denoise(lrhip_ctx *ctx, const lrhip_denoise_params *params, const floa
 int lrhip_aov_denoise(lrhip_ctx *ctx, const lrhip_denoise_params *params, uint32_t component, uint32_t samples, float *out);
 /* HIP-event time of the kernels (prepare, the passes, finish) of the last lrhip_denoise / lrhip_aov_denoise call, in ms */
 double lrhip_last_denoise_ms(lrhip_ctx *ctx);
+
+/* Ray queries: closest hit or occlusion for caller-supplied rays against the scene of the last lrhip_upload_scene /
+ * lrhip_update_scene, on the renderers' own traversal loop.  The reference has no such entry point (its Geometry::trace_closest /
+ * trace_any are only reachable from inside a kernel, src/base/geometry.cpp:218-279).  Camera, integrator and sampler play no part;
+ * LRHIP_ERROR_INVALID before any scene has been uploaded.
+ *   What can be hit   the baked BVH triangles of VISIBLE instances (lr_instance.visible, baked flag bit 0), exactly as in the renderer.
+ *   A hit             has t_min < t < t_max, both strict; t_max = +inf is allowed.  Directions need not be normalised: t is in units of
+ *                     |d|.  u, v: the weights of the triangle's second and third vertex; inst, prim: the instance and primitive ids of
+ *                     the renderer's hit record (lr_scene.instances, the primitive within its mesh); tri indexes lr_scene.accel.triangles;
+ *                     reserved is written 0.
+ *   A miss            t = +inf, u = v = 0, inst = prim = tri = LR_INVALID_ID.
+ *   LRHIP_RAY_ANY     stops at the first accepted triangle: out[i] = 1 (occluded) or 0.
+ *   Screened rays     a ray with a non-finite component (t_max = +inf is the one exception), a zero direction, or for which
+ *                     t_max > t_min is false is a miss / not occluded; it never enters the traversal loop.
+ *   Alpha test        without LRHIP_RAY_ALPHA_TEST every visible triangle is opaque.  With it, candidates on maybe-non-opaque instances
+ *                     pass through the scene's stochastic alpha test exactly as in the renderer (Geometry::_alpha_skip: a hash of instance,
+ *                     primitive and the barycentric bits against the surface's opacity there).  Ignored for scenes with any_non_opaque == 0.
+ *   Pointers          with LRHIP_RAY_DEVICE_POINTERS both are device memory, 16-byte aligned (else LRHIP_ERROR_INVALID), and the call is
+ *                     asynchronous on the context's stream.  Without it both are host memory: the library stages them through context-owned
+ *                     buffers (they grow on demand up to 32 MiB each and are released with the context; a larger batch goes through them
+ *                     chunk by chunk) and the call synchronises.
+ *   Determinism       a ray's result is a function of the ray and the scene only: bit-identical from run to run and wherever the ray
+ *                     stands in the batch.                                                                                          */
+typedef struct lrhip_ray { float o[3], t_min, d[3], t_max; } lrhip_ray;                                       /* 32 bytes */
+typedef struct lrhip_ray_hit { float t, u, v; uint32_t inst, prim, tri, reserved[2]; } lrhip_ray_hit;         /* 32 bytes */
+typedef struct lrhip_ray_query_params {
+    const void *rays;  /* lrhip_ray[count] */
+    void *out;         /* LRHIP_RAY_CLOSEST: lrhip_ray_hit[count]; LRHIP_RAY_ANY: uint32_t[count] (1 occluded, 0 not) */
+    uint64_t count;    /* 0 is legal and launches nothing; at most 2^31 - 1 */
+    uint32_t mode;     /* LRHIP_RAY_CLOSEST or LRHIP_RAY_ANY */
+    uint32_t flags;    /* LRHIP_RAY_DEVICE_POINTERS, LRHIP_RAY_ALPHA_TEST */
+} lrhip_ray_query_params;
+#define LRHIP_RAY_CLOSEST 0u
+#define LRHIP_RAY_ANY 1u
+#define LRHIP_RAY_DEVICE_POINTERS 1u
+#define LRHIP_RAY_ALPHA_TEST 2u
+#define LRHIP_RAY_MAX_COUNT 0x7fffffffull
+int lrhip_trace_rays(lrhip_ctx *ctx, const lrhip_ray_query_params *params);
+/* HIP-event time of the kernel(s) of the last lrhip_trace_rays call (a host-pointer call: summed over its chunks), in ms; synchronises */
+double lrhip_last_trace_ms(lrhip_ctx *ctx);
 
 /* The path's only collective: sum-reduce of the per-rank films to rank `root` over RCCL / xGMI, in place on the film
  * this context accumulates into, in stream order behind the renders.  `nccl_comm` is the caller's ncclComm_t (one per process /

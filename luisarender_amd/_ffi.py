@@ -135,7 +135,27 @@ class DenoiseParams(C.Structure):
 
 DENOISE_DEMODULATE = 1  # LRHIP_DENOISE_DEMODULATE
 
-STRUCTS = {"lrhip_denoise_params": DenoiseParams, "lr_scene": Scene, "lr_vertex": Vertex, "lr_triangle": Triangle, "lr_alias_entry": AliasEntry,
+
+class Ray(C.Structure):
+    """lrhip_ray (include/lrhip.h): one row of the [N, 8] float32 array MegaPathRenderer.trace takes"""
+    _fields_ = [("o", f32 * 3), ("t_min", f32), ("d", f32 * 3), ("t_max", f32)]
+
+
+class RayHit(C.Structure):
+    """lrhip_ray_hit (include/lrhip.h): one row of the [N, 8] 32-bit buffer behind RayHits"""
+    _fields_ = [("t", f32), ("u", f32), ("v", f32), ("inst", u32), ("prim", u32), ("tri", u32), ("reserved", u32 * 2)]
+
+
+class RayQueryParams(C.Structure):
+    """lrhip_ray_query_params (include/lrhip.h)"""
+    _fields_ = [("rays", C.c_void_p), ("out", C.c_void_p), ("count", u64), ("mode", u32), ("flags", u32)]
+
+
+RAY_CLOSEST, RAY_ANY = 0, 1  # LRHIP_RAY_CLOSEST / LRHIP_RAY_ANY
+RAY_DEVICE_POINTERS, RAY_ALPHA_TEST = 1, 2  # LRHIP_RAY_DEVICE_POINTERS / LRHIP_RAY_ALPHA_TEST
+
+STRUCTS = {"lrhip_denoise_params": DenoiseParams, "lrhip_ray": Ray, "lrhip_ray_hit": RayHit, "lrhip_ray_query_params": RayQueryParams,
+           "lr_scene": Scene, "lr_vertex": Vertex, "lr_triangle": Triangle, "lr_alias_entry": AliasEntry,
            "lr_mesh": Mesh, "lr_instance": Instance, "lr_texture": Texture, "lr_surface": Surface,
            "lr_light": Light, "lr_environment": Environment, "lr_camera": Camera, "lr_filter": Filter,
            "lr_film": Film, "lr_sampler": Sampler, "lr_integrator": Integrator, "lr_bvh4_node": Bvh4Node,
@@ -244,5 +264,8 @@ def hip_lib(path: str | None = None) -> C.CDLL:
         lib.lrhip_aov_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_uint32, C.c_uint32, C.c_void_p]
         lib.lrhip_last_denoise_ms.restype = C.c_double
         lib.lrhip_last_denoise_ms.argtypes = [C.c_void_p]
+        lib.lrhip_trace_rays.argtypes = [C.c_void_p, C.POINTER(RayQueryParams)]
+        lib.lrhip_last_trace_ms.restype = C.c_double
+        lib.lrhip_last_trace_ms.argtypes = [C.c_void_p]
         lib._lr_ready = True
     return lib

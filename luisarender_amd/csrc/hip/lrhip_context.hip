@@ -109,6 +109,9 @@ void lrhip_destroy(lrhip_ctx *ctx) {
     ctx->denoise_guide.release(), ctx->denoise_colour[0].release(), ctx->denoise_colour[1].release(), ctx->denoise_inputs.release();
     if (ctx->denoise_begin) { (void)hipEventDestroy(ctx->denoise_begin); }
     if (ctx->denoise_end) { (void)hipEventDestroy(ctx->denoise_end); }
+    ctx->raycast_rays.release(), ctx->raycast_out.release();
+    if (ctx->raycast_begin) { (void)hipEventDestroy(ctx->raycast_begin); }
+    if (ctx->raycast_end) { (void)hipEventDestroy(ctx->raycast_end); }
     ctx->spill.release(), ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->wf_counts.release(), ctx->wf_accum.release();
     ctx->pool.release(), ctx->counters.release(), ctx->work_counter.release(), ctx->scene_record.release();
     if (ctx->ev_begin) { (void)hipEventDestroy(ctx->ev_begin); }

@@ -8,6 +8,7 @@
 //   lrhip_wavefront.hip  the host loop of wavefront mode
 //   lrhip_comm.hip       the RCCL collectives
 //   lrhip_denoise.hip    the edge-avoiding wavelet filter over the AOV buffers (denoise_kernels.h)
+//   lrhip_raycast.hip    ray queries: closest hit / occlusion for caller-supplied rays (raycast_kernel.h)
 // Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
 #pragma once
 #include "../../../include/lrhip.h"
@@ -158,6 +159,14 @@ struct lrhip_ctx {
     lrh::DeviceBuffer denoise_guide, denoise_colour[2], denoise_inputs;
     hipEvent_t denoise_begin{nullptr}, denoise_end{nullptr};// around the kernels of the last call (lrhip_last_denoise_ms); made on first use
     bool denoise_timed{false};
+    // ray queries (lrhip_raycast.hip): the staging buffers of a host-pointer call (one chunk of rays, one of results; they grow on demand
+    // and outlive the scene), the events around the last launch, the kernel time of the last call's finished launches and whether one is
+    // still to be read (lrhip_last_trace_ms), resident blocks per CU of the two kernels (alpha test off / on; -1: not asked yet)
+    lrh::DeviceBuffer raycast_rays, raycast_out;
+    hipEvent_t raycast_begin{nullptr}, raycast_end{nullptr};
+    double raycast_ms{0.};
+    bool raycast_pending{false};
+    int raycast_blocks[2]{-1, -1};
 };
 
 namespace lrh {

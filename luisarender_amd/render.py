@@ -36,6 +36,60 @@ def aov_file_name(camera_file: str, component: str, n: int, dump: str) -> str:
     return os.path.join(parent, f"{stem}_{component}{'' if dump == 'final' else f'_{n:05d}'}{ext}")
 
 
+def check_rays(rays, device: int | None = None) -> str:
+    """What MegaPathRenderer.trace accepts (no device needed): a C-contiguous float32 numpy array [N, 8] laid out (ox, oy, oz, t_min,
+    dx, dy, dz, t_max) -> "numpy", or a contiguous float32 torch tensor of that shape on GPU `device` (None: any GPU) -> "torch".
+    ValueError for anything else."""
+    if isinstance(rays, np.ndarray):
+        kind = "numpy"
+        contiguous = rays.flags["C_CONTIGUOUS"]
+        is_float32 = rays.dtype == np.float32
+    elif type(rays).__module__.split(".")[0] == "torch" and hasattr(rays, "data_ptr"):
+        import torch
+        kind = "torch"
+        contiguous = rays.is_contiguous()
+        is_float32 = rays.dtype == torch.float32
+        if rays.device.type != "cuda":
+            raise ValueError(f"trace: the ray tensor is on {rays.device}, not on a GPU")
+        if device is not None and rays.device.index != device:
+            raise ValueError(f"trace: the ray tensor is on {rays.device}, the renderer on GPU {device}")
+    else:
+        raise ValueError(f"trace: rays must be a numpy array or a torch tensor, not {type(rays).__name__}")
+    if not is_float32:
+        raise ValueError(f"trace: rays must be float32, not {rays.dtype}")
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError(f"trace: rays must have shape [N, 8] (ox, oy, oz, t_min, dx, dy, dz, t_max), not {tuple(rays.shape)}")
+    if not contiguous:
+        raise ValueError("trace: rays must be contiguous")
+    return kind
+
+
+class RayHits:
+    """Closest hits of MegaPathRenderer.trace: views (no copies) of ONE [N, 8] 32-bit buffer of lrhip_ray_hit records -- `buffer`, a
+    float32 numpy array or, for the torch path, the float32 tensor on the device.  t (+inf: a miss), u, v: float32; inst, prim, tri:
+    uint32 (torch: int32, LR_INVALID_ID reads -1); hit = inst != 0xffffffff."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        if isinstance(buffer, np.ndarray):
+            ids = buffer.view(np.uint32)
+            invalid = np.uint32(0xFFFFFFFF)
+        else:
+            import torch
+            ids = buffer.view(torch.int32)
+            invalid = -1
+        self.t, self.u, self.v = buffer[:, 0], buffer[:, 1], buffer[:, 2]
+        self.inst, self.prim, self.tri = ids[:, 3], ids[:, 4], ids[:, 5]
+        self._invalid = invalid
+
+    @property
+    def hit(self):
+        return self.inst != self._invalid
+
+    def __len__(self) -> int:
+        return int(self.buffer.shape[0])
+
+
 class MegaPathRenderer:
     """One lrhip_ctx on one GPU.  Mirrors the reference's ProgressiveIntegrator::Instance::render
     (src/base/integrator.cpp:34-49): prepare film -> render spp -> download (convert) -> save."""
@@ -43,6 +97,7 @@ class MegaPathRenderer:
     def __init__(self, device: int = 0, lib_path: str | None = None):
         self._lib = _ffi.hip_lib(lib_path)  # raises if liblrhip.so is missing: there is no CPU fallback
         self._ctx = C.c_void_p()
+        self._device = device
         self._check(self._lib.lrhip_create(device, C.byref(self._ctx)))
         self._scene = None
         self.width = self.height = 0
@@ -161,6 +216,38 @@ class MegaPathRenderer:
 
     def last_denoise_ms(self) -> float:
         return float(self._lib.lrhip_last_denoise_ms(self._ctx))
+
+    def trace(self, rays, any_hit: bool = False, alpha_test: bool = False, sync: bool = True):
+        """lrhip_trace_rays (lrhip.h has the semantics): closest hit or occlusion of caller-supplied rays against the uploaded scene.
+        rays: what check_rays accepts.  A numpy array goes through host pointers (the call synchronises).  A torch tensor on this
+        renderer's GPU is read in place and the result is a tensor on that device, without a copy through the host: torch's current
+        stream is synchronised before the call and the context after it; a caller who has bound the context to torch's stream
+        (set_stream) may pass sync=False.  Returns RayHits, or with any_hit a bool array / tensor [N] (True: occluded)."""
+        kind = check_rays(rays, self._device)
+        n = int(rays.shape[0])
+        p = _ffi.RayQueryParams()
+        p.count = n
+        p.mode = _ffi.RAY_ANY if any_hit else _ffi.RAY_CLOSEST
+        p.flags = _ffi.RAY_ALPHA_TEST if alpha_test else 0
+        if kind == "numpy":
+            out = np.empty(n, np.uint32) if any_hit else np.empty((n, 8), np.float32)
+            p.rays, p.out = rays.ctypes.data, out.ctypes.data
+            self._check(self._lib.lrhip_trace_rays(self._ctx, C.byref(p)))
+            return out != 0 if any_hit else RayHits(out)
+        import torch
+        out = torch.empty(n, dtype=torch.int32, device=rays.device) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+        p.rays, p.out = rays.data_ptr(), out.data_ptr()
+        p.flags |= _ffi.RAY_DEVICE_POINTERS
+        if sync:
+            torch.cuda.current_stream(rays.device).synchronize()
+        self._check(self._lib.lrhip_trace_rays(self._ctx, C.byref(p)))
+        if sync:
+            self.synchronize()
+        return out != 0 if any_hit else RayHits(out)
+
+    def last_trace_ms(self) -> float:
+        """lrhip_last_trace_ms: HIP-event time of the kernel(s) of the last trace()"""
+        return float(self._lib.lrhip_last_trace_ms(self._ctx))
 
     # ---- the one collective of the multi-GPU path (SURVEY 8e), through the C ABI
     def comm_unique_id(self) -> bytes:
