@@ -17,6 +17,7 @@
  *   lrhip_film_download            ColorFilmInstance::download            src/films/color.cpp:99-105
  *   lrhip_film_reduce              (no reference equivalent: the one collective of the multi-GPU path)
  *   lrhip_trace_rays               (no reference entry point: Geometry::trace_closest / trace_any for the caller's rays)
+ *   lrhip_trace_radiance           (no reference entry point: MegakernelPathTracingInstance::Li for the caller's rays)
  *   lrhip_get_counters             (no reference equivalent; roofline accounting)
  *
  * Conventions: 0 = OK, negative = error (text via lrhip_last_error, thread-local); nothing
@@ -196,6 +197,58 @@ int lrhip_trace_rays(lrhip_ctx *ctx, const lrhip_ray_query_params *params);
 /* HIP-event time of the kernel(s) of the last lrhip_trace_rays call (a host-pointer call: summed over its chunks), in ms; synchronises */
 double lrhip_last_trace_ms(lrhip_ctx *ctx);
 
+/* Radiance queries: the radiance that arrives along caller-supplied rays, by the MegaPath estimator of the scene of the last
+ * lrhip_upload_scene / lrhip_update_scene (at the time it was moved to) -- lightmap and probe baking, cameras the scene format does not have,
+ * radiance for a batch of rays, a re-render of a few pixels.  The reference's Li is only reachable through a scene's camera and film.
+ *   Estimator      sample s of ray k is MegakernelPathTracingInstance::Li (src/integrators/mega_path.cpp:49-156) with the caller's ray in place
+ *                  of camera.generate_ray, and nothing else changed: the throughput starts at 1 and pdf_bsdf at 1e16 (emission and environment
+ *                  seen directly are unweighted); depth, rr_depth and rr_threshold are the uploaded scene's integrator's; the shutter weight is 1.
+ *                  t_min and t_max bound the first segment only.  Directions need not be normalised: shading takes wo = -d / |d|, so the
+ *                  kernel divides |d| out of the direction and multiplies t_min and t_max by it -- the segment is the caller's; a direction
+ *                  whose squared length is within 4e-7 of 1 (what a float normalisation returns) is taken bit for bit.  Any finite non-zero
+ *                  direction will do, denormal or near FLT_MAX: an end of the segment whose distance in units of the unit vector is beyond
+ *                  the float range becomes +inf, one below it 0.
+ *   Sampler        ray k has the stream id j = streams ? streams[k] : k.  Its sampler is started exactly as Li starts it for pixel
+ *                  (j mod W, (j div W) mod H) of the scene's camera frame W x H at sample index s, then draws and discards what Li draws before
+ *                  its first bounce: generate_pixel_2d, and generate_2d for the lens iff the scene's camera is a thin lens.  So a ray that IS
+ *                  camera ray (px, py, s), queried with stream py W + px at sample s, walks the path the film's sample walks.  Two rays with
+ *                  the same j at the same s share their random numbers; for j >= W H the stream wraps (no error).
+ *   Accumulation   per sample ColorFilmInstance::_accumulate (src/films/color.cpp:107-130) into the ray's record (sum r, sum g, sum b, n), the
+ *                  film's layout: a sample with a NaN or infinite component is rejected, the others are clamped to `clamp` and n += 1.  Without
+ *                  LRHIP_RADIANCE_ACCUMULATE the library zeroes `out` first; with it the sums are added to what `out` holds (progressive
+ *                  refinement over calls with disjoint sample ranges).
+ *   Screened rays  a ray lrhip_trace_rays would screen (a non-finite component other than t_max = +inf, a zero direction, t_max > t_min false)
+ *                  starts no path: its record is (0, 0, 0, 0), or untouched under LRHIP_RADIANCE_ACCUMULATE.  n = 0 tells.
+ *   No lighting    a scene with neither lights nor an environment renders nothing in the reference (mega_path.cpp:40-47: "no lights in scene",
+ *                  the film stays black with n = 0) and in lrhip_render.  Here too: nothing is launched, every record is (0, 0, 0, 0), or
+ *                  untouched under LRHIP_RADIANCE_ACCUMULATE, and the call returns LRHIP_OK.
+ *   Pointers       as for lrhip_trace_rays.  With LRHIP_RAY_DEVICE_POINTERS rays and out are 16-byte aligned device memory, streams 4-byte
+ *                  aligned (else LRHIP_ERROR_INVALID), and the call is asynchronous on the context's stream.  Without it all three are host
+ *                  memory, staged through context-owned buffers 2^20 rays at a time, and the call synchronises.
+ *   Determinism    the same call gives the same bits from run to run.  With ONE sample per call a ray's record is a function of (ray, stream id,
+ *                  s, scene) only, wherever the ray stands in the batch.  With several samples per call the adds of one ray happen in the order
+ *                  its paths finish, which depends on the 63 rays of its work item, and the sample range is cut into chunks by a rule of (count,
+ *                  sample range) only: across batch layouts the result is the same up to the order of float additions, no more.
+ *   Scope          scenes whose integrator is MegaPath, nested Mix / Layered surfaces included; LRHIP_ERROR_UNSUPPORTED for AOV, Direct, Normal
+ *                  and MegaVPTNaive scenes, LRHIP_ERROR_INVALID before any upload, for NULL rays / out with count > 0 and for misaligned device
+ *                  pointers.  One kernel serves every MegaPath scene -- the all-closures one-path-per-lane kernel -- so a scene without Mix /
+ *                  Layered surfaces is queried more slowly than lrhip_render renders it.  lrhip_last_variant keeps reporting the last lrhip_render.
+ *   Counters       LRHIP_RADIANCE_COUNTERS runs the counting twin and adds to lrhip_get_counters; `paths` counts the valid rays x samples. */
+typedef struct lrhip_radiance_query_params {
+    const void *rays;      /* lrhip_ray[count], as for lrhip_trace_rays */
+    const void *streams;   /* uint32_t[count] or NULL (= 0, 1, 2, ...): the sampler stream of each ray */
+    void *out;             /* float4[count]: (sum r, sum g, sum b, n) per ray */
+    uint64_t count;        /* 0 is legal and launches nothing; at most LRHIP_RAY_MAX_COUNT */
+    uint32_t spp_begin, spp_end;  /* sample indices [begin, end) of every ray; begin >= end launches nothing */
+    uint32_t flags;        /* LRHIP_RAY_DEVICE_POINTERS, LRHIP_RADIANCE_ACCUMULATE, LRHIP_RADIANCE_COUNTERS */
+    float clamp;           /* per-sample radiance clamp; 0 = the uploaded scene's film clamp */
+} lrhip_radiance_query_params;
+#define LRHIP_RADIANCE_ACCUMULATE 4u
+#define LRHIP_RADIANCE_COUNTERS 8u
+int lrhip_trace_radiance(lrhip_ctx *ctx, const lrhip_radiance_query_params *params);
+/* HIP-event time of the kernel(s) of the last lrhip_trace_radiance call (a host-pointer call: summed over its chunks), in ms; synchronises */
+double lrhip_last_radiance_ms(lrhip_ctx *ctx);
+
 /* The path's only collective: sum-reduce of the per-rank films to rank `root` over RCCL / xGMI, in place on the film
  * this context accumulates into, in stream order behind the renders.  `nccl_comm` is the caller's ncclComm_t (one per process /
  * GPU, created by the caller: ncclCommInitRank); librccl.so is loaded on first use, so the library has no link-time dependency
@@ -240,6 +293,7 @@ double lrhip_last_render_ms(lrhip_ctx *ctx);
 #define LRHIP_FEAT_VOLUMETRIC 256u
 #define LRHIP_FEAT_NESTED 512u /* Mix trees with Layered leaves / Layered surfaces with Mix interfaces */
 #define LRHIP_FEAT_AOV 32768u  /* the AOV integrator's kernels (lrhip_last_variant: with the all-closures scene bits) */
+#define LRHIP_FEAT_QUERY 65536u /* the radiance-query kernels (lrhip_trace_radiance; never reported by lrhip_last_variant) */
 uint32_t lrhip_last_variant(lrhip_ctx *ctx);
 
 /* Diagnostics of ONE context, for tests and tools (the product path never calls it; the library reads no environment variable):

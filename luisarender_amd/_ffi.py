@@ -151,10 +151,19 @@ class RayQueryParams(C.Structure):
     _fields_ = [("rays", C.c_void_p), ("out", C.c_void_p), ("count", u64), ("mode", u32), ("flags", u32)]
 
 
+class RadianceQueryParams(C.Structure):
+    """lrhip_radiance_query_params (include/lrhip.h)"""
+    _fields_ = [("rays", C.c_void_p), ("streams", C.c_void_p), ("out", C.c_void_p), ("count", u64), ("spp_begin", u32), ("spp_end", u32),
+                ("flags", u32), ("clamp", f32)]
+
+
 RAY_CLOSEST, RAY_ANY = 0, 1  # LRHIP_RAY_CLOSEST / LRHIP_RAY_ANY
 RAY_DEVICE_POINTERS, RAY_ALPHA_TEST = 1, 2  # LRHIP_RAY_DEVICE_POINTERS / LRHIP_RAY_ALPHA_TEST
+RADIANCE_ACCUMULATE, RADIANCE_COUNTERS = 4, 8  # LRHIP_RADIANCE_ACCUMULATE / LRHIP_RADIANCE_COUNTERS
+FEAT_QUERY = 65536  # LRHIP_FEAT_QUERY
 
 STRUCTS = {"lrhip_denoise_params": DenoiseParams, "lrhip_ray": Ray, "lrhip_ray_hit": RayHit, "lrhip_ray_query_params": RayQueryParams,
+           "lrhip_radiance_query_params": RadianceQueryParams,
            "lr_scene": Scene, "lr_vertex": Vertex, "lr_triangle": Triangle, "lr_alias_entry": AliasEntry,
            "lr_mesh": Mesh, "lr_instance": Instance, "lr_texture": Texture, "lr_surface": Surface,
            "lr_light": Light, "lr_environment": Environment, "lr_camera": Camera, "lr_filter": Filter,
@@ -267,5 +276,8 @@ def hip_lib(path: str | None = None) -> C.CDLL:
         lib.lrhip_trace_rays.argtypes = [C.c_void_p, C.POINTER(RayQueryParams)]
         lib.lrhip_last_trace_ms.restype = C.c_double
         lib.lrhip_last_trace_ms.argtypes = [C.c_void_p]
+        lib.lrhip_trace_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceQueryParams)]
+        lib.lrhip_last_radiance_ms.restype = C.c_double
+        lib.lrhip_last_radiance_ms.argtypes = [C.c_void_p]
         lib._lr_ready = True
     return lib

@@ -246,6 +246,12 @@ struct RenderArgs {
     // of the launch (waves out of items while the last ones finish) short.  Uniform chunks: chunk_big_count = chunk_count.
     uint32_t chunk_big_count, chunk_big, chunk_small;
     float4 *pool;          // pool kernels (megapool_kernel.h): path state of every thread's two contexts, [context][quad][thread], Infinity-Cache resident
+    // radiance queries (kFeatQuery kernels only; lrhip_radiance.hip): "tile" t of a launch is rays [64 t, 64 t + 64) of the batch
+    const float4 *query_rays;     // lrhip_ray[query_count]: (o, t_min), (d, t_max)
+    const uint32_t *query_streams;// sampler stream of each ray, or nullptr: ray k has stream query_stream_base + k
+    float4 *query_out;            // (sum r, sum g, sum b, n) per ray
+    uint32_t query_count;         // < 2^31
+    uint32_t query_stream_base;   // (a host-pointer call goes through the staging buffers chunk by chunk: the chunk's first ray)
 };
 
 // item number -> (tile of the range, chunk, sample range) under the chunking above

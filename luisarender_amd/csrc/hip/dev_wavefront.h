@@ -33,6 +33,10 @@ enum : uint32_t {
     // the AOV integrator (src/integrators/aov.cpp): auxiliary buffers summed per wave in LDS (dev_wavefront.h: aov_add), on top of the
     // all-closures scene mask only; the one-path-per-lane kernel with a second throughput / radiance for the diffuse split, no Russian roulette
     kFeatAov = 32768u,
+    // radiance queries (lrhip.h: lrhip_trace_radiance): the all-closures one-path-per-lane kernel whose work items are 64
+    // consecutive caller-supplied rays instead of an 8x8 tile -- the path starts from the caller's ray instead of the camera's, its sums go
+    // to the ray's record instead of the film
+    kFeatQuery = 65536u,
     kFeatSceneMask = kFeatEnv | kFeatAlpha | kFeatDisney | kFeatMix | kFeatLayered
 };
 

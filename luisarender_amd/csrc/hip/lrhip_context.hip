@@ -52,6 +52,14 @@ hipError_t launch_resolve_aov_partial(lrhip_ctx *ctx, uint32_t chunk_count, uint
     return hipGetLastError();
 }
 
+// The same reduce over the records of a radiance query: one row of `count` "pixels".  The frame is declared 2^31 wide with 2^28 tile columns, so
+// that record i < 2^31 is pixel (i, 0) of tile i / 8 in row 0 -- whose rotation is none -- and every tile is in the range [0, 2^32 - 1) at stride 1
+hipError_t launch_resolve_records(lrhip_ctx *ctx, float4 *records, const float4 *partial, uint32_t count, uint32_t chunk_count) {
+    hipLaunchKernelGGL(lrd::resolve_partial_kernel, dim3((count + 255u) / 256u), dim3(256), 0, ctx->stream, records, partial, count, chunk_count,
+                       0x80000000u, 1u << 28u, 0u, 0xffffffffu, 1u);
+    return hipGetLastError();
+}
+
 // the frame's fixed-point sums join the film (and are cleared for the next call)
 hipError_t launch_wf_resolve(lrhip_ctx *ctx, double inv_scale) {
     const auto pixel_count = ctx->width * ctx->height;
@@ -112,6 +120,9 @@ void lrhip_destroy(lrhip_ctx *ctx) {
     ctx->raycast_rays.release(), ctx->raycast_out.release();
     if (ctx->raycast_begin) { (void)hipEventDestroy(ctx->raycast_begin); }
     if (ctx->raycast_end) { (void)hipEventDestroy(ctx->raycast_end); }
+    ctx->radiance_streams.release(), ctx->radiance_out.release();
+    if (ctx->radiance_begin) { (void)hipEventDestroy(ctx->radiance_begin); }
+    if (ctx->radiance_end) { (void)hipEventDestroy(ctx->radiance_end); }
     ctx->spill.release(), ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->wf_counts.release(), ctx->wf_accum.release();
     ctx->pool.release(), ctx->counters.release(), ctx->work_counter.release(), ctx->scene_record.release();
     if (ctx->ev_begin) { (void)hipEventDestroy(ctx->ev_begin); }

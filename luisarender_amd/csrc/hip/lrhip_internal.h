@@ -9,6 +9,7 @@
 //   lrhip_comm.hip       the RCCL collectives
 //   lrhip_denoise.hip    the edge-avoiding wavelet filter over the AOV buffers (denoise_kernels.h)
 //   lrhip_raycast.hip    ray queries: closest hit / occlusion for caller-supplied rays (raycast_kernel.h)
+//   lrhip_radiance.hip   radiance queries: MegaPath's estimator along caller-supplied rays (the kFeatQuery kernels of megapath_kernel.h)
 // Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
 #pragma once
 #include "../../../include/lrhip.h"
@@ -167,6 +168,13 @@ struct lrhip_ctx {
     double raycast_ms{0.};
     bool raycast_pending{false};
     int raycast_blocks[2]{-1, -1};
+    // radiance queries (lrhip_radiance.hip): a host-pointer call stages its rays through raycast_rays above, its stream ids and records through
+    // these two (they grow on demand and outlive the scene); the events around the last launch, the kernel time of the last call's finished
+    // launches and whether one is still to be read (lrhip_last_radiance_ms).  The chunks' partial planes are `partial`, the film kernels' own
+    lrh::DeviceBuffer radiance_streams, radiance_out;
+    hipEvent_t radiance_begin{nullptr}, radiance_end{nullptr};
+    double radiance_ms{0.};
+    bool radiance_pending{false};
 };
 
 namespace lrh {
@@ -205,6 +213,8 @@ hipError_t launch_resolve_partial(lrhip_ctx *ctx, const float4 *partial, uint32_
 hipError_t launch_resolve_aov_partial(lrhip_ctx *ctx, uint32_t chunk_count, uint32_t tiles_x, uint32_t tile_begin, uint32_t tile_end,
                                       uint32_t tile_stride);
 hipError_t launch_wf_resolve(lrhip_ctx *ctx, double inv_scale);
+// resolve_partial_kernel over a "frame" of `count` records instead of the film's pixels (radiance queries): records[i] += sum of partial[c][i]
+hipError_t launch_resolve_records(lrhip_ctx *ctx, float4 *records, const float4 *partial, uint32_t count, uint32_t chunk_count);
 hipError_t launch_wf_carry(lrhip_ctx *ctx, uint32_t margin, uint32_t mode);
 
 }// namespace lrh

@@ -19,12 +19,13 @@ namespace lrh {
 const KernelEntry kKernels[kKernelCount] = {LR_MEGAKERNEL_LIST(LR_VARIANT_ENTRY) LR_HEAVY_LIST(LR_HEAVY_ENTRY)};
 
 // variants.h against lrd::kSceneVariants, at compile time: the search below may name any kSceneVariants[i] x {counters} x {generic sampler},
-// and the padded / AOV kernels are asked for by their defining bit
+// and the padded / AOV / query kernels are asked for by their defining bit
 namespace {
 #define LR_MASK(mask) mask##u,
 constexpr uint32_t kListedVariants[] = {LR_VARIANT_LIST(LR_MASK)};
 constexpr uint32_t kListedPadded[] = {LR_PADDED_LIST(LR_MASK)};
 constexpr uint32_t kListedAov[] = {LR_AOV_LIST(LR_MASK)};
+constexpr uint32_t kListedQuery[] = {LR_QUERY_LIST(LR_MASK)};
 #undef LR_MASK
 constexpr bool scene_variants_are_listed() {
     for (auto scene : lrd::kSceneVariants) {
@@ -48,6 +49,8 @@ static_assert(all_carry(kListedPadded, lrd::kFeatPadded | lrd::kFeatGeneric | lr
     "variants.h: LR_PADDED_LIST holds PaddedSobol pool kernels");
 static_assert(all_carry(kListedAov, lrd::kFeatAov | lrd::kFeatSceneMask),
     "variants.h: LR_AOV_LIST holds kFeatAov kernels on the all-closures mask");
+static_assert(all_carry(kListedQuery, lrd::kFeatQuery | lrd::kFeatSceneMask),
+    "variants.h: LR_QUERY_LIST holds kFeatQuery kernels on the all-closures mask");
 }// namespace
 
 const KernelEntry *find_kernel(uint32_t mask, bool heavy) {

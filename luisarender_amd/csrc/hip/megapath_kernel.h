@@ -20,6 +20,7 @@
 // (src/films/color.cpp:107-130).
 #pragma once
 #include "dev_wavefront.h"
+#include "raycast_kernel.h"// (raycast_ray_valid: the screening of a caller's ray)
 
 namespace lrd {
 
@@ -49,6 +50,10 @@ namespace lrd {
 //   kFeatAov      the AOV integrator (src/integrators/aov.cpp:237-366), also on top of the all-features variant only: a second throughput
 //                 and radiance for the diffuse part, first-hit buffers, no Russian roulette; its sums go to per-wave LDS tiles of the
 //                 enabled channels (dynamic LDS: megapath_variant.hip) and from there to scene.aov like the film's (lrhip_aov_download)
+//   kFeatQuery    radiance queries (lrhip.h: lrhip_trace_radiance), also on top of the all-features variant only: a work item is 64 consecutive
+//                 caller-supplied rays x a sample chunk instead of an 8x8 tile x a sample chunk; a path starts from the caller's ray (two
+//                 dwordx4 loads, raycast_kernel.h's screening) with the sampler of the ray's stream id, and the item's LDS tile is added to the
+//                 rays' records instead of the film.  Everything between the prologue and the epilogue is the film kernel's
 // the precompiled scene-feature sets, smallest first (each also exists x {Count} x {Generic}); csrc/hip/variants/*.hip
 constexpr uint32_t kSceneVariants[] = {
     0u,
@@ -137,8 +142,9 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
     constexpr bool COUNT = (F & kFeatCount) != 0u, PCG = (F & kFeatGeneric) != 0u, ENV = (F & kFeatEnv) != 0u,
                    ALPHA = (F & kFeatAlpha) != 0u, DISNEY = (F & kFeatDisney) != 0u, MIX = (F & kFeatMix) != 0u,
                    LAYERED = (F & kFeatLayered) != 0u, AUX = (F & kFeatAux) != 0u, WF = (F & kFeatWf) != 0u, CONT = (F & kFeatCont) != 0u,
-                   AOV = (F & kFeatAov) != 0u;
+                   AOV = (F & kFeatAov) != 0u, QUERY = (F & kFeatQuery) != 0u;
     static_assert(!AOV || (MIX && LAYERED && !AUX && !WF), "the AOV kernel is the all-closures one-path-per-lane kernel");
+    static_assert(!QUERY || (MIX && LAYERED && !AUX && !WF && !AOV), "the query kernel is the all-closures one-path-per-lane kernel");
     static_assert(!LAYERED || DISNEY, "the Layered interpreter instantiates the Disney closure");
     // (Disney inline in the wavefront kernels, only Mix / Layered parked, was measured: C5 at 512 spp 442 -> 386 Msamples/s -- the lean
     // kernel pays 109 spilled VGPRs for it, profiles/archive/r03i_wavefront_ab.txt)
@@ -497,6 +503,48 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                         sampler.restore(scene, words);
                         path_open = true;
                     }
+                } else if constexpr (QUERY) {
+                    // the same prologue with the caller's ray in place of camera.generate_ray: ray 64 * tile_index + (k & 63) of the batch, sample
+                    // s_begin + (k >> 6).  The sampler is the one of pixel (j mod W, (j div W) mod H) for the ray's stream id j, moved past what
+                    // Li draws before its first bounce (the pixel sample, the lens sample of a thin lens): a ray that IS that pixel's camera ray
+                    // walks the film's path.  A ray beyond the batch's end or screened out (raycast_ray_valid) starts no path: n stays as it is
+                    const auto index = tile_index * 64u + (k & 63u);
+                    if (need && k < q_total && index < args.query_count) {
+                        pixel = film_tile + (k & 63u);
+                        const auto rp = args.query_rays + static_cast<size_t>(index) * 2u;
+                        const auto a = rp[0], b = rp[1];
+                        if (raycast_ray_valid(a, b)) {
+                            const auto j = args.query_streams != nullptr ? args.query_streams[index] : args.query_stream_base + index;
+                            px = j % scene.camera.width, py = (j / scene.camera.width) % scene.camera.height;
+                            sampler.start(scene, px, py, s_begin + (k >> 6u));
+                            (void)sampler.next_pixel_2d();
+                            if (scene.camera.kind == LR_CAMERA_THIN_LENS) { (void)sampler.next_2d(); }
+                            // shading takes wo = -d as a unit vector: any other length is divided out here and t_min, t_max follow, so that the
+                            // segment is the caller's.  A direction that is unit length to within rounding (what normalize() returns) is taken
+                            // bit for bit
+                            auto d = mk3(b.x, b.y, b.z);
+                            auto t_min = a.w, t_max = b.w;
+                            if (!(fabsf(dot(d, d) - 1.f) <= 4e-7f)) {
+                                // any finite non-zero d (the screening lets denormals and FLT_MAX through): a power of two first brings its largest
+                                // component into 2^-60 .. 2^60 -- exact, and neither the squares nor the hardware's reciprocal and square root
+                                // meet a denormal or overflow -- and the interval's ends take |d| in two factors, so that no product is 0 x inf
+                                const auto m = fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
+                                const auto pre = m < 0x1p-40f ? 0x1p100f : (m > 0x1p40f ? 0x1p-100f : 1.f);
+                                const auto unpre = m < 0x1p-40f ? 0x1p-100f : (m > 0x1p40f ? 0x1p100f : 1.f);
+                                const auto dp = d * pre;
+                                const auto len = sqrtf(dot(dp, dp));
+                                d = dp * (1.f / len);
+                                t_min = (t_min * len) * unpre, t_max = (t_max * len) * unpre;
+                            }
+                            ray = Ray{mk3(a.x, a.y, a.z), t_min, d, t_max};
+                            beta = mk3(1.f);
+                            Li = mk3(0.f);
+                            pdf_bsdf = 1e16f;
+                            depth = 0u;
+                            path_open = true, want_closest = true;
+                            if (COUNT) { local.paths++; }
+                        }
+                    }
                 } else if (need && k < q_total) {// MegakernelPathTracingInstance::Li prologue, mega_path.cpp:52-62
                     const auto pix = k & 63u;
                     px = tx * 8u + (pix & 7u), py = ty * 8u + (pix >> 3u);
@@ -560,7 +608,19 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
         }
         // ---- item complete: lane l adds pixel l of the tile to the film (or stores this chunk's partial plane)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (!CONT) {
+        if constexpr (QUERY) {// lane l adds its sums to ray 64 * tile_index + l's record (or stores this chunk's partial plane over the batch)
+            const auto index = tile_index * 64u + lane;
+            if (index < args.query_count) {
+                const auto acc = film_tile[lane];
+                if (args.chunk_count == 1u) {
+                    auto f = args.query_out[index];
+                    f.x += acc.x, f.y += acc.y, f.z += acc.z, f.w += acc.w;
+                    args.query_out[index] = f;
+                } else {
+                    args.partial[static_cast<size_t>(chunk) * args.query_count + index] = acc;
+                }
+            }
+        } else if (!CONT) {
             const auto wx = tx * 8u + (lane & 7u), wy = ty * 8u + (lane >> 3u);
             if (wx < scene.camera.width && wy < scene.camera.height) {
                 const auto acc = film_tile[lane];

@@ -47,8 +47,13 @@
 // megapath_variant.hip), and the selection rule asks for them by mask for AOV scenes only
 #define LR_AOV_LIST(X) X(32892) X(32893) X(32894) X(32895)
 
+// radiance queries (kFeatQuery = 65536, lrhip_trace_radiance): the all-closures scene mask with its counting and generic-sampler
+// twins, and once more with kFeatNest (512) for scenes whose Mix / Layered surfaces nest.  Not part of kSceneVariants: lrhip_trace_radiance asks
+// for them by mask, lrhip_render never does
+#define LR_QUERY_LIST(X) X(65660) X(65661) X(65662) X(65663) X(66172) X(66173) X(66174) X(66175)
+
 // every object built from megapath_variant.hip
-#define LR_MEGAKERNEL_LIST(X) LR_VARIANT_LIST(X) LR_PADDED_LIST(X) LR_AOV_LIST(X)
+#define LR_MEGAKERNEL_LIST(X) LR_VARIANT_LIST(X) LR_PADDED_LIST(X) LR_AOV_LIST(X) LR_QUERY_LIST(X)
 
 // the heavy-closure kernels of wavefront mode (heavy_kernel.h; heavy_variant.hip, -DLR_HVARIANT=<mask>): bit 0 counters, bit 1 generic sampler,
 // bits 2-3 the closure kind (0 Disney, 4 Mix, 8 Layered), 512 Mix / Layered nested in each other

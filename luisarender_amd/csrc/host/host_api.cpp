@@ -157,7 +157,7 @@ uint64_t lrhost_sizeof(const char *name) {
     LR_SIZEOF(lr_camera) LR_SIZEOF(lr_filter) LR_SIZEOF(lr_film) LR_SIZEOF(lr_sampler) LR_SIZEOF(lr_integrator)
     LR_SIZEOF(lr_bvh4_node) LR_SIZEOF(lr_bvh_triangle) LR_SIZEOF(lr_accel) LR_SIZEOF(lr_light_handle)
     LR_SIZEOF(lr_medium) LR_SIZEOF(lrhip_denoise_params)
-    LR_SIZEOF(lrhip_ray) LR_SIZEOF(lrhip_ray_hit) LR_SIZEOF(lrhip_ray_query_params)
+    LR_SIZEOF(lrhip_ray) LR_SIZEOF(lrhip_ray_hit) LR_SIZEOF(lrhip_ray_query_params) LR_SIZEOF(lrhip_radiance_query_params)
 #undef LR_SIZEOF
     return 0u;
 }

@@ -64,6 +64,43 @@ def check_rays(rays, device: int | None = None) -> str:
     return kind
 
 
+def check_radiance_args(rays, spp: int = 1, spp_begin: int = 0, streams=None, clamp=None, accumulate_into=None, device: int | None = None) -> str:
+    """What MegaPathRenderer.radiance accepts besides check_rays' rays (no device needed): spp, spp_begin >= 0 with spp_begin + spp < 2^32;
+    streams None or uint32 (torch: int32, read as uint32) of shape [N]; clamp None or a positive finite number; accumulate_into None or a float32
+    raw result [N, 4].  streams and accumulate_into are of the same kind as rays (numpy / torch on the same GPU) and contiguous.  Returns
+    check_rays' answer; ValueError for anything else."""
+    kind = check_rays(rays, device)
+    n = int(rays.shape[0])
+    if isinstance(spp, bool) or isinstance(spp_begin, bool) or not isinstance(spp, (int, np.integer)) or not isinstance(spp_begin, (int, np.integer)):
+        raise ValueError("radiance: spp and spp_begin must be integers")
+    if spp < 0 or spp_begin < 0 or spp_begin + spp > 0xFFFFFFFF:
+        raise ValueError(f"radiance: samples [{spp_begin}, {spp_begin} + {spp}) are not a range of 32-bit sample indices")
+    if clamp is not None and not (0.0 < float(clamp) < float("inf")):
+        raise ValueError(f"radiance: clamp must be a positive finite number or None (the scene's film clamp), not {clamp}")
+
+    def check(name, a, shape, dtype_name):
+        if kind == "numpy":
+            ok_kind = isinstance(a, np.ndarray)
+        else:
+            ok_kind = type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
+        if not ok_kind:
+            raise ValueError(f"radiance: {name} must be a {kind} array like rays, not {type(a).__name__}")
+        if kind == "torch" and a.device != rays.device:
+            raise ValueError(f"radiance: {name} is on {a.device}, rays on {rays.device}")
+        if str(a.dtype).split(".")[-1] != dtype_name:
+            raise ValueError(f"radiance: {name} must be {dtype_name}, not {a.dtype}")
+        if tuple(a.shape) != shape:
+            raise ValueError(f"radiance: {name} must have shape {list(shape)}, not {tuple(a.shape)}")
+        if not (a.flags["C_CONTIGUOUS"] if kind == "numpy" else a.is_contiguous()):
+            raise ValueError(f"radiance: {name} must be contiguous")
+
+    if streams is not None:
+        check("streams", streams, (n,), "uint32" if kind == "numpy" else "int32")
+    if accumulate_into is not None:
+        check("accumulate_into", accumulate_into, (n, 4), "float32")
+    return kind
+
+
 class RayHits:
     """Closest hits of MegaPathRenderer.trace: views (no copies) of ONE [N, 8] 32-bit buffer of lrhip_ray_hit records -- `buffer`, a
     float32 numpy array or, for the torch path, the float32 tensor on the device.  t (+inf: a miss), u, v: float32; inst, prim, tri:
@@ -248,6 +285,45 @@ class MegaPathRenderer:
     def last_trace_ms(self) -> float:
         """lrhip_last_trace_ms: HIP-event time of the kernel(s) of the last trace()"""
         return float(self._lib.lrhip_last_trace_ms(self._ctx))
+
+    def radiance(self, rays, spp: int = 1, spp_begin: int = 0, streams=None, clamp: float | None = None, accumulate_into=None,
+                 raw: bool = False, counters: bool = False, sync: bool = True):
+        """lrhip_trace_radiance (lrhip.h has the semantics): MegaPath's radiance estimate along caller-supplied rays, samples
+        [spp_begin, spp_begin + spp) of each.  rays, streams, accumulate_into: what check_radiance_args accepts; numpy arrays go through host
+        pointers, torch tensors on this renderer's GPU are read in place and the result stays on the device (synchronisation as in trace()).
+        streams: the sampler stream of each ray (None: 0, 1, 2, ...; stream py * W + px is pixel (px, py)'s).  clamp: per-sample clamp (None:
+        the scene's film clamp).  accumulate_into: a previous raw result, refined IN PLACE by these samples and returned.  Returns the [N, 3]
+        means sum / max(n, 1), or with raw the [N, 4] sums (sum r, sum g, sum b, n).  counters: the counting kernel (counters())."""
+        kind = check_radiance_args(rays, spp, spp_begin, streams, clamp, accumulate_into, self._device)
+        n = int(rays.shape[0])
+        p = _ffi.RadianceQueryParams()
+        p.count = n
+        p.spp_begin, p.spp_end = spp_begin, spp_begin + spp
+        p.clamp = 0.0 if clamp is None else clamp
+        p.flags = (_ffi.RADIANCE_ACCUMULATE if accumulate_into is not None else 0) | (_ffi.RADIANCE_COUNTERS if counters else 0)
+        if kind == "numpy":
+            out = accumulate_into if accumulate_into is not None else np.empty((n, 4), np.float32)
+            p.rays, p.out = rays.ctypes.data, out.ctypes.data
+            p.streams = streams.ctypes.data if streams is not None else None
+            self._check(self._lib.lrhip_trace_radiance(self._ctx, C.byref(p)))
+            return out if raw else out[:, :3] / np.maximum(out[:, 3:4], np.float32(1.0))
+        import torch
+        out = accumulate_into if accumulate_into is not None else torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        if n != 0 and (rays.data_ptr() % 16 != 0 or out.data_ptr() % 16 != 0):
+            raise ValueError("radiance: rays and accumulate_into must be 16-byte aligned on the device")
+        p.rays, p.out = rays.data_ptr(), out.data_ptr()
+        p.streams = streams.data_ptr() if streams is not None else None
+        p.flags |= _ffi.RAY_DEVICE_POINTERS
+        if sync:
+            torch.cuda.current_stream(rays.device).synchronize()
+        self._check(self._lib.lrhip_trace_radiance(self._ctx, C.byref(p)))
+        if sync:
+            self.synchronize()
+        return out if raw else out[:, :3] / torch.clamp(out[:, 3:4], min=1.0)
+
+    def last_radiance_ms(self) -> float:
+        """lrhip_last_radiance_ms: HIP-event time of the kernel(s) of the last radiance()"""
+        return float(self._lib.lrhip_last_radiance_ms(self._ctx))
 
     # ---- the one collective of the multi-GPU path (SURVEY 8e), through the C ABI
     def comm_unique_id(self) -> bytes:
