@@ -104,6 +104,10 @@ HIP_OBJ := $(patsubst $(HIPDIR)/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
 # the variants' safe flag.  RAYCAST_DEFS: its A/B builds (make hip-variant NAME=r64 RAYCAST_DEFS=-DLR_RAYCAST_REFILL=64 VARIANT_MASKS=0 HEAVY_MASKS=)
 RAYCAST_DEFS ?=
 lrhip_raycast_FLAGS = $(CALL_SAFE_FLAGS) $(RAYCAST_DEFS)
+# lrhip_instance_update.o holds the kernels that move instances on the device (csrc/hip/instance_update_kernels.h).  Their tables are held to the
+# host's unfused fp32 code bit for bit (tests/test_gpu_instance_transforms.py), and HIPFLAGS gives none of what that takes: no fp contraction,
+# correctly rounded fp32 division (normal_matrix's 1 / det, quantise_node's scale), no approximate functions (-fapprox-func also marks divisions)
+lrhip_instance_update_FLAGS = -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-approx-func
 $(HIP_OBJ): $(OBJDIR)/%.o: $(HIPDIR)/%.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $($*_FLAGS) -c -o $@ $<

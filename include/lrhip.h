@@ -18,6 +18,7 @@
  *   lrhip_film_reduce              (no reference equivalent: the one collective of the multi-GPU path)
  *   lrhip_trace_rays               (no reference entry point: Geometry::trace_closest / trace_any for the caller's rays)
  *   lrhip_trace_radiance           (no reference entry point: MegakernelPathTracingInstance::Li for the caller's rays)
+ *   lrhip_set_instance_transforms  (Geometry::update for matrices the caller holds, computed on the device)
  *   lrhip_get_counters             (no reference equivalent; roofline accounting)
  *
  * Conventions: 0 = OK, negative = error (text via lrhip_last_error, thread-local); nothing
@@ -249,6 +250,38 @@ int lrhip_trace_radiance(lrhip_ctx *ctx, const lrhip_radiance_query_params *para
 /* HIP-event time of the kernel(s) of the last lrhip_trace_radiance call (a host-pointer call: summed over its chunks), in ms; synchronises */
 double lrhip_last_radiance_ms(lrhip_ctx *ctx);
 
+/* Moving instances on the device: Geometry::update (src/base/geometry.cpp:194-216) for object-to-world matrices the caller holds --
+ * an animation frame, a physics step whose matrices are a tensor on the GPU, a drag in an editor -- between two renders or queries, without a
+ * trip of the tables through the host.
+ *   What it rewrites  the four device tables lrhip_update_scene rewrites for moved geometry: the instance records (matrix and normal matrix), the
+ *                     baked BVH triangles of the listed instances, their shading records, and every BVH packet, refitted over the same topology
+ *                     and quantised again.  Afterwards they hold, bit for bit, what lrhip_update_scene would have written for the uploaded scene
+ *                     with exactly these matrices in lr_instance.object_to_world, re-baked and refitted by the host (lrhost_scene_set_instance_transforms).
+ *                     Film, AOV buffers, counters, camera, environment, textures, lights and the selected kernels stay as they are.  The call is
+ *                     ordered on the context's stream behind earlier renders and queries and before later ones.
+ *   Matrices          float[count][16], column-major: element [4 c + r] is row r of column c, the layout of lr_instance.object_to_world; the
+ *                     fourth row is not read.  instances: the id of each matrix's instance (an index into lr_scene.instances), or NULL for ids
+ *                     0 .. count-1 (then count <= instance_count).  Instances that are not listed keep their matrices.
+ *   Pointers          without LRHIP_RAY_DEVICE_POINTERS both arrays are host memory: ids are checked to be in range and distinct, every matrix
+ *                     element to be finite (else LRHIP_ERROR_INVALID, nothing changed), they are staged through a context-owned buffer, and the
+ *                     call synchronises.  With it both are device memory, the matrices 16-byte and the ids 4-byte aligned (else
+ *                     LRHIP_ERROR_INVALID), and the call is asynchronous on the context's stream: an id out of range is skipped, of several
+ *                     entries with one id the last one wins, and a non-finite matrix gives non-finite tables -- the caller's error, but no fault.
+ *   The host scene    the caller's lr_scene is not read and does not change.  A later lrhip_update_scene or lrhip_upload_scene overwrites what
+ *                     this call wrote: the host's tables win again.  A caller who keeps both in step moves the host scene by
+ *                     lrhost_scene_set_instance_transforms.
+ *   Errors            LRHIP_ERROR_INVALID before any upload, for NULL matrices with count > 0, unknown flags and count > 2^31 - 1;
+ *                     LRHIP_ERROR_UNSUPPORTED for a BVH whose nodes are not stored parents first (lrhost_scene_build_accel's are).             */
+typedef struct lrhip_instance_update_params {
+    const void *object_to_world; /* float[count][16], column-major, the layout of lr_instance.object_to_world */
+    const void *instances;       /* uint32_t[count] instance ids, or NULL: ids 0 .. count-1 */
+    uint64_t count;              /* 0 is legal and launches nothing; with instances == NULL at most instance_count */
+    uint32_t flags;              /* LRHIP_RAY_DEVICE_POINTERS */
+} lrhip_instance_update_params;
+int lrhip_set_instance_transforms(lrhip_ctx *ctx, const lrhip_instance_update_params *params);
+/* HIP-event time of the kernels of the last lrhip_set_instance_transforms call, in ms; synchronises */
+double lrhip_last_instance_update_ms(lrhip_ctx *ctx);
+
 /* The path's only collective: sum-reduce of the per-rank films to rank `root` over RCCL / xGMI, in place on the film
  * this context accumulates into, in stream order behind the renders.  `nccl_comm` is the caller's ncclComm_t (one per process /
  * GPU, created by the caller: ncclCommInitRank); librccl.so is loaded on first use, so the library has no link-time dependency
@@ -393,6 +426,18 @@ uint32_t lrhip_pool_auto_triangles(uint32_t max_depth, uint32_t scene_spp);
 #define LRHIP_PLAN_WORDS 8
 int lrhip_plan_kernels(uint32_t features, uint32_t force_features, uint32_t flags, uint32_t sampler_kind, uint32_t wf_mode, uint32_t max_depth,
                        uint32_t out[LRHIP_PLAN_WORDS]);
+
+/* TEST HOOK (the product path never calls it): `bytes` bytes from `byte_offset` of one of the four device tables that move with the geometry,
+ * as lrhip_upload_scene / lrhip_update_scene / lrhip_set_instance_transforms left them, copied to `out`.  Synchronises.  The tables: the
+ * 64-byte BVH packets; the 48-byte baked triangles and, behind the last one, the all-zero sentinel the empty node slots name; the 128-byte
+ * instance records; the 128-byte shading records.  LRHIP_ERROR_INVALID before any upload and for a range that is not inside the table.    */
+#define LRHIP_TABLE_NODES 0u
+#define LRHIP_TABLE_BVH_TRIANGLES 1u
+#define LRHIP_TABLE_INSTANCES 2u
+#define LRHIP_TABLE_SHADE_TRIANGLES 3u
+int lrhip_read_scene_table(lrhip_ctx *ctx, uint32_t which, uint64_t byte_offset, uint64_t bytes, void *out);
+/* size in bytes of that table in the uploaded scene (0: none, or an unknown table) */
+uint64_t lrhip_scene_table_bytes(lrhip_ctx *ctx, uint32_t which);
 
 const char *lrhip_last_error(void);
 

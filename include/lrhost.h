@@ -41,6 +41,14 @@ int lrhost_scene_build_accel(lrhost_scene *scene);
  *   and refits the BVH when it is built; the tables behind lrhost_scene_view change in place (*updated = whether anything
  *   moved: upload the scene again then). */
 int lrhost_scene_set_time(lrhost_scene *scene, float time, int *updated);
+/* Moving instances by matrices the caller holds (Geometry::update, geometry.cpp:194-216; the host mirror of lrhip.h's
+ * lrhip_set_instance_transforms): object_to_world[i] -- float[16], column-major, the layout of lr_instance.object_to_world -- becomes the
+ * matrix of instance instances[i], or of instance i when `instances` is NULL (then count <= instance_count).  The baked triangles of
+ * these instances are re-baked and the BVH is refitted over the same topology when it is built; the tables behind lrhost_scene_view
+ * change in place (upload the scene again, or lrhip_update_scene).  An error, with nothing changed, for an id out of range or listed
+ * twice, a non-finite matrix element, or NULL matrices with count > 0.  A later lrhost_scene_set_time moves the instances that carry
+ * an animated transform to their transform's value again; the others keep what this call gave them.                              */
+int lrhost_scene_set_instance_transforms(lrhost_scene *scene, uint64_t count, const uint32_t *instances, const float *object_to_world);
 int lrhost_scene_shutter_sample_count(const lrhost_scene *scene, int camera_index);
 int lrhost_scene_shutter_sample(const lrhost_scene *scene, int camera_index, int sample_index, float *time, float *weight, uint32_t *spp);
 int lrhost_scene_camera_count(const lrhost_scene *scene);

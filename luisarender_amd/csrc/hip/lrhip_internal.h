@@ -10,6 +10,7 @@
 //   lrhip_denoise.hip    the edge-avoiding wavelet filter over the AOV buffers (denoise_kernels.h)
 //   lrhip_raycast.hip    ray queries: closest hit / occlusion for caller-supplied rays (raycast_kernel.h)
 //   lrhip_radiance.hip   radiance queries: MegaPath's estimator along caller-supplied rays (the kFeatQuery kernels of megapath_kernel.h)
+//   lrhip_instance_update.hip  moving instances on the device: re-bake, refit and re-quantise (instance_update_kernels.h); the table test hook
 // Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
 #pragma once
 #include "../../../include/lrhip.h"
@@ -175,6 +176,19 @@ struct lrhip_ctx {
     hipEvent_t radiance_begin{nullptr}, radiance_end{nullptr};
     double radiance_ms{0.};
     bool radiance_pending{false};
+    // moving instances (lrhip_instance_update.hip).  Of the uploaded scene (in scene_buffers): the fp32 boxes of the BVH the packets are
+    // quantised from, refitted in place, and the node indices sorted by level of the tree -- level l is level_nodes[level_offsets[l] ..
+    // level_offsets[l + 1]); empty level_offsets: the node order does not allow a refit (a child before its parent).  Of the context: the
+    // staging buffer of a host-pointer call (matrices, then ids), the call's scratch (owner word per instance, then the moved-instance
+    // bits), the events around the last call's kernels, and its kernel time once read (lrhip_last_instance_update_ms)
+    lr_bvh4_node *nodes32{nullptr};
+    const uint32_t *level_nodes{nullptr};
+    std::vector<uint32_t> level_offsets;
+    uint64_t vertex_count{0u};
+    lrh::DeviceBuffer update_stage, update_scratch;
+    hipEvent_t update_begin{nullptr}, update_end{nullptr};
+    double update_ms{0.};
+    bool update_pending{false};
 };
 
 namespace lrh {

@@ -363,6 +363,38 @@ int upload_sampler_tables(lrhip_ctx *ctx, const lr_scene *s) {
     return LRHIP_OK;
 }
 
+// what lrhip_set_instance_transforms refits the tree from (lrhip_instance_update.hip): the fp32 boxes and the nodes by level.  refit_accel
+// (csrc/host/accel.cpp) walks the nodes from the last to the first because children have larger indices than their parents; the same property
+// gives every node a level in one ascending pass.  A tree without it is rendered like any other, but cannot be refitted on the device
+int upload_refit_tables(lrhip_ctx *ctx, const lr_scene *s) {
+    const lr_bvh4_node *nodes32 = nullptr;
+    LR_UP(upload(ctx, s->accel.nodes, s->accel.node_count, &nodes32));
+    ctx->nodes32 = const_cast<lr_bvh4_node *>(nodes32);
+    ctx->vertex_count = s->vertex_count;
+    const auto n = s->accel.node_count;
+    std::vector<uint32_t> level(n, 0u);
+    auto depth = 0u;
+    auto ordered = true;
+    for (uint32_t i = 0u; i < n && ordered; i++) {
+        for (auto c : s->accel.nodes[i].child) {
+            if (c == LR_INVALID_ID || (c & 0x80000000u) != 0u) { continue; }
+            if (c <= i || c >= n) { ordered = false; break; }
+            level[c] = std::max(level[c], level[i] + 1u);
+        }
+        depth = std::max(depth, level[i]);
+    }
+    ctx->level_offsets.clear();
+    if (!ordered) { return LRHIP_OK; }
+    std::vector<uint32_t> offsets(depth + 2u, 0u), sorted(n);
+    for (uint32_t i = 0u; i < n; i++) { offsets[level[i] + 1u]++; }
+    for (size_t l = 1u; l < offsets.size(); l++) { offsets[l] += offsets[l - 1u]; }
+    auto next = offsets;
+    for (uint32_t i = 0u; i < n; i++) { sorted[next[level[i]]++] = i; }
+    LR_UP(upload(ctx, sorted.data(), sorted.size(), &ctx->level_nodes));
+    ctx->level_offsets = std::move(offsets);
+    return LRHIP_OK;
+}
+
 // everything lrhip_upload_scene puts on the device and into ctx->scene, step by step
 int upload_scene_tables(lrhip_ctx *ctx, const lr_scene *s) {
     auto &d = ctx->scene;
@@ -371,6 +403,7 @@ int upload_scene_tables(lrhip_ctx *ctx, const lr_scene *s) {
         auto packed = build_packed_nodes(s);
         LR_UP(upload(ctx, packed.data(), packed.size(), &d.nodes));
     }
+    LR_UP(upload_refit_tables(ctx, s));
     {
         auto padded = build_padded_triangles(s);
         const uint8_t *dev = nullptr;
@@ -528,6 +561,8 @@ int lrhip_update_scene(lrhip_ctx *ctx, const lr_scene *s) {
     LR_HIP_CHECK(copy(d.bvh_tris, padded.data(), padded.size()));
     LR_HIP_CHECK(copy(d.instances, instances.data(), instances.size() * sizeof(instances[0])));
     LR_HIP_CHECK(copy(d.shade_tris, shade.data(), shade.size() * sizeof(shade[0])));
+    // the fp32 boxes a later lrhip_set_instance_transforms refits from: the host's tables win again
+    LR_HIP_CHECK(copy(ctx->nodes32, s->accel.nodes, static_cast<size_t>(s->accel.node_count) * sizeof(lr_bvh4_node)));
     LR_HIP_CHECK(hipStreamSynchronize(ctx->stream));// the host vectors above go out of scope
     set_camera(d, s);
     if (d.env_kind == lrd::kEnvConstant) {

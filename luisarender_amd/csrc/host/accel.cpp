@@ -549,6 +549,11 @@ void build_accel(SceneData &scene) {
 void refit_accel(SceneData &scene) {
     std::vector<char> moved(scene.instances.size(), 0);
     for (auto &d : scene.dynamic_instances) { moved[d.instance] = 1; }
+    refit_accel(scene, moved);
+}
+
+// the same for the instances marked in `moved` (one flag per instance): set_scene_instance_transforms marks the ones its caller lists
+void refit_accel(SceneData &scene, const std::vector<char> &moved) {
     for (auto &bt : scene.bvh_triangles) {
         if (!moved[bt.inst]) { continue; }
         auto &inst = scene.instances[bt.inst];

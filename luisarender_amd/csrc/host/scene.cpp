@@ -1714,6 +1714,32 @@ bool set_scene_time(SceneData &scene, float time) {
     return moved;
 }
 
+void set_scene_instance_transforms(SceneData &scene, uint64_t count, const uint32_t *ids, const float *matrices) {
+    const auto instance_count = scene.instances.size();
+    if (count != 0u && matrices == nullptr) { throw Error{"Instance transforms: the matrices are NULL."}; }
+    if (ids == nullptr && count > instance_count) {
+        throw Error{"Instance transforms: " + std::to_string(count) + " matrices without ids for " + std::to_string(instance_count) + " instances."};
+    }
+    std::vector<char> moved(instance_count, 0);
+    for (uint64_t i = 0u; i < count; i++) {
+        const auto id = ids != nullptr ? ids[i] : static_cast<uint32_t>(i);
+        if (id >= instance_count) { throw Error{"Instance transforms: instance id " + std::to_string(id) + " out of range."}; }
+        if (moved[id] != 0) { throw Error{"Instance transforms: instance id " + std::to_string(id) + " is listed twice."}; }
+        moved[id] = 1;
+        for (auto k = 0u; k < 16u; k++) {
+            if (!std::isfinite(matrices[i * 16u + k])) {
+                throw Error{"Instance transforms: matrix " + std::to_string(i) + " has a non-finite element."};
+            }
+        }
+    }
+    if (count == 0u) { return; }
+    for (uint64_t i = 0u; i < count; i++) {
+        const auto id = ids != nullptr ? ids[i] : static_cast<uint32_t>(i);
+        std::memcpy(scene.instances[id].object_to_world, matrices + i * 16u, sizeof(float) * 16u);
+    }
+    if (!scene.bvh_nodes.empty()) { refit_accel(scene, moved); }
+}
+
 std::unique_ptr<SceneData> build_scene(const SceneDesc &desc) {
     auto out = std::make_unique<SceneData>();
     Builder{desc, *out}.build();

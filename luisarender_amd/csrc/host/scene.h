@@ -119,12 +119,17 @@ void build_environment_tables(const SceneData &scene, lr_environment &env, std::
 void build_accel(SceneData &scene);
 // accel.cpp: re-bake the triangles of moved instances and refit the boxes of the existing BVH (same topology)
 void refit_accel(SceneData &scene);
+void refit_accel(SceneData &scene, const std::vector<char> &moved);// ... of the instances with moved[instance] != 0
 
 // scene.cpp: evaluate a compiled transform (Transform::matrix(time))
 float4x4 evaluate_xform(const SceneData &scene, uint32_t id, float time);
 // scene.cpp: Pipeline::update (pipeline.cpp:101-113) + Geometry::update (geometry.cpp:194-216): re-evaluate every animated
 // transform at `time` (instances, cameras, environment), refit the BVH if it is built; returns whether anything moved
 bool set_scene_time(SceneData &scene, float time);
+// scene.cpp: Geometry::update for matrices the caller holds: object_to_world of instance ids[i] (ids == nullptr: instance i) becomes
+// matrices[i] (column-major, the layout of lr_instance.object_to_world), and the BVH is refitted for these instances if it is built.  Throws
+// on an id out of range or listed twice, a non-finite element, or more matrices than instances without ids; nothing has changed then
+void set_scene_instance_transforms(SceneData &scene, uint64_t count, const uint32_t *ids, const float *matrices);
 
 // mesh_io.cpp: OBJ loader standing in for assimp (src/shapes/mesh.cpp:46-69 flag semantics)
 struct LoadedMesh {

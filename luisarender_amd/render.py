@@ -101,6 +101,65 @@ def check_radiance_args(rays, spp: int = 1, spp_begin: int = 0, streams=None, cl
     return kind
 
 
+def check_instance_transforms(matrices, instances=None, instance_count: int | None = None, device: int | None = None) -> str:
+    """What MegaPathRenderer.set_instance_transforms and Scene.set_instance_transforms accept (no device needed).  matrices: float32,
+    contiguous, [N, 4, 4] or [N, 16] in COLUMN-MAJOR storage -- matrices[i, c, r] (flat: [i, 4 c + r]) is row r of column c, the layout of
+    lr_instance.object_to_world; a numpy row-major 4 x 4 matrix M goes in as M.T.  instances: None (matrix i moves instance i; then
+    N <= instance_count) or the N instance ids, a one-dimensional integer array.  A numpy array -> "numpy": every element finite, every id
+    in [0, instance_count) and listed once (the range checks need instance_count).  A torch tensor on GPU `device` (None: any GPU) ->
+    "torch": ids int32 on the same device; values on the device are not looked at (the kernel skips an id out of range).  matrices and
+    instances are of the same kind.  ValueError for anything else."""
+    what = "set_instance_transforms"
+    if isinstance(matrices, np.ndarray):
+        kind = "numpy"
+        contiguous = matrices.flags["C_CONTIGUOUS"]
+        is_float32 = matrices.dtype == np.float32
+    elif type(matrices).__module__.split(".")[0] == "torch" and hasattr(matrices, "data_ptr"):
+        import torch
+        kind = "torch"
+        contiguous = matrices.is_contiguous()
+        is_float32 = matrices.dtype == torch.float32
+        if matrices.device.type != "cuda":
+            raise ValueError(f"{what}: the matrix tensor is on {matrices.device}, not on a GPU")
+        if device is not None and matrices.device.index != device:
+            raise ValueError(f"{what}: the matrix tensor is on {matrices.device}, the renderer on GPU {device}")
+    else:
+        raise ValueError(f"{what}: matrices must be a numpy array or a torch tensor, not {type(matrices).__name__}")
+    if not is_float32:
+        raise ValueError(f"{what}: matrices must be float32, not {matrices.dtype}")
+    shape = tuple(matrices.shape)
+    if not ((len(shape) == 3 and shape[1:] == (4, 4)) or (len(shape) == 2 and shape[1] == 16)):
+        raise ValueError(f"{what}: matrices must have shape [N, 4, 4] or [N, 16] (column-major), not {shape}")
+    if not contiguous:
+        raise ValueError(f"{what}: matrices must be contiguous")
+    n = shape[0]
+    if kind == "numpy" and not np.isfinite(matrices).all():
+        raise ValueError(f"{what}: a matrix has a non-finite element")
+    if instances is None:
+        if instance_count is not None and n > instance_count:
+            raise ValueError(f"{what}: {n} matrices without ids for {instance_count} instances")
+        return kind
+    if kind == "numpy":
+        if not isinstance(instances, np.ndarray) or instances.dtype.kind not in "iu":
+            raise ValueError(f"{what}: instances must be an integer numpy array like matrices")
+    else:
+        import torch
+        if not (type(instances).__module__.split(".")[0] == "torch" and hasattr(instances, "data_ptr")) or instances.dtype != torch.int32:
+            raise ValueError(f"{what}: instances must be an int32 torch tensor like matrices")
+        if instances.device != matrices.device:
+            raise ValueError(f"{what}: instances is on {instances.device}, matrices on {matrices.device}")
+        if not instances.is_contiguous():
+            raise ValueError(f"{what}: instances must be contiguous")
+    if tuple(instances.shape) != (n,):
+        raise ValueError(f"{what}: instances must have shape [{n}], not {tuple(instances.shape)}")
+    if kind == "numpy":
+        if n and (int(instances.min()) < 0 or int(instances.max()) > 0xFFFFFFFF or (instance_count is not None and int(instances.max()) >= instance_count)):
+            raise ValueError(f"{what}: an instance id is out of range")
+        if np.unique(instances).size != n:
+            raise ValueError(f"{what}: an instance id is listed twice")
+    return kind
+
+
 class RayHits:
     """Closest hits of MegaPathRenderer.trace: views (no copies) of ONE [N, 8] 32-bit buffer of lrhip_ray_hit records -- `buffer`, a
     float32 numpy array or, for the torch path, the float32 tensor on the device.  t (+inf: a miss), u, v: float32; inst, prim, tri:
@@ -324,6 +383,46 @@ class MegaPathRenderer:
     def last_radiance_ms(self) -> float:
         """lrhip_last_radiance_ms: HIP-event time of the kernel(s) of the last radiance()"""
         return float(self._lib.lrhip_last_radiance_ms(self._ctx))
+
+    def set_instance_transforms(self, matrices, instances=None, sync: bool = True) -> None:
+        """lrhip_set_instance_transforms (lrhip.h has the semantics): move instances of the uploaded scene on the device -- their records, baked
+        triangles and shading records are rewritten and the BVH is refitted and quantised again, in stream order behind earlier renders and
+        queries; film, counters and everything else stay.  matrices, instances: what check_instance_transforms accepts -- float32 [N, 4, 4]
+        or [N, 16] in COLUMN-MAJOR storage (a numpy row-major matrix M goes in as M.T), and the N instance ids or None for instances
+        0 .. N-1.  numpy arrays go through host pointers (checked, the call synchronises).  torch tensors on this renderer's GPU are read in
+        place and the call is asynchronous on the context's stream: torch's current stream is synchronised before it; sync=False skips that
+        for a caller who has bound the context to torch's stream (set_stream).  The host Scene is not touched: a later upload() of it, with
+        or without keep_film, brings the host's tables back; Scene.set_instance_transforms keeps it in step."""
+        count = int(self._scene.view().instance_count) if self._scene is not None else None
+        kind = check_instance_transforms(matrices, instances, count, self._device)
+        p = _ffi.InstanceUpdateParams()
+        p.count = int(matrices.shape[0])
+        if kind == "numpy":
+            ids = np.ascontiguousarray(instances, dtype=np.uint32) if instances is not None else None
+            p.object_to_world = matrices.ctypes.data
+            p.instances = ids.ctypes.data if ids is not None else None
+            self._check(self._lib.lrhip_set_instance_transforms(self._ctx, C.byref(p)))
+            return
+        import torch
+        p.object_to_world = matrices.data_ptr()
+        p.instances = instances.data_ptr() if instances is not None else None
+        p.flags = _ffi.RAY_DEVICE_POINTERS
+        if sync:
+            torch.cuda.current_stream(matrices.device).synchronize()
+        self._check(self._lib.lrhip_set_instance_transforms(self._ctx, C.byref(p)))
+
+    def last_instance_update_ms(self) -> float:
+        """lrhip_last_instance_update_ms: HIP-event time of the kernels of the last set_instance_transforms()"""
+        return float(self._lib.lrhip_last_instance_update_ms(self._ctx))
+
+    def scene_table(self, which: int) -> np.ndarray:
+        """tests / tools only (lrhip_read_scene_table): the bytes of one of the device tables that move with the geometry
+        (_ffi.TABLE_NODES, TABLE_BVH_TRIANGLES -- with the sentinel behind the last triangle --, TABLE_INSTANCES, TABLE_SHADE_TRIANGLES)
+        as a uint8 array [records, bytes per record]"""
+        size = int(self._lib.lrhip_scene_table_bytes(self._ctx, which))
+        out = np.empty(size, np.uint8)
+        self._check(self._lib.lrhip_read_scene_table(self._ctx, which, 0, size, out.ctypes.data))
+        return out.reshape(-1, _ffi.TABLE_RECORD_BYTES[which])
 
     # ---- the one collective of the multi-GPU path (SURVEY 8e), through the C ABI
     def comm_unique_id(self) -> bytes:

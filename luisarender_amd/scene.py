@@ -78,6 +78,22 @@ class Scene:
         self._views.clear()
         return bool(updated.value)
 
+    def set_instance_transforms(self, matrices, instances=None) -> None:
+        """lrhost_scene_set_instance_transforms: the host mirror of MegaPathRenderer.set_instance_transforms -- matrices[i] becomes the
+        object-to-world matrix of instance instances[i] (None: of instance i), the moved instances are re-baked and the BVH is refitted when
+        it is built; the tables behind view() change in place (upload again, with keep_film to carry the film on).  matrices: a float32 numpy
+        array [N, 4, 4] or [N, 16] in COLUMN-MAJOR storage, the layout of lr_instance.object_to_world (a numpy row-major matrix M goes in as
+        M.T); instances: N integer ids or None (render.check_instance_transforms has the rules)."""
+        from .render import check_instance_transforms
+        if check_instance_transforms(matrices, instances, int(self.view().instance_count)) != "numpy":
+            raise ValueError("set_instance_transforms: the host scene takes numpy arrays")
+        ids = np.ascontiguousarray(instances, dtype=np.uint32) if instances is not None else None
+        rc = self._lib.lrhost_scene_set_instance_transforms(self._handle, int(matrices.shape[0]), ids.ctypes.data if ids is not None else None,
+                                                            matrices.ctypes.data)
+        if rc != 0:
+            raise HostError(self._lib.lrhost_last_error().decode())
+        self._views.clear()
+
     def shutter_samples(self, camera: int = 0) -> list[tuple[float, float, int]]:
         """Camera::shutter_samples (src/base/camera.cpp:163-203) -> [(time, weight, spp)]"""
         out = []
