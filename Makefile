@@ -108,6 +108,9 @@ lrhip_raycast_FLAGS = $(CALL_SAFE_FLAGS) $(RAYCAST_DEFS)
 # host's unfused fp32 code bit for bit (tests/test_gpu_instance_transforms.py), and HIPFLAGS gives none of what that takes: no fp contraction,
 # correctly rounded fp32 division (normal_matrix's 1 / det, quantise_node's scale), no approximate functions (-fapprox-func also marks divisions)
 lrhip_instance_update_FLAGS = -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-approx-func
+# lrhip_mesh_update.o holds the kernels that deform a mesh in front of those (csrc/hip/mesh_update_kernels.h); its normal recompute -- sums of cross
+# products, one square root, three divisions -- is held to the host's bits in the same way (tests/test_gpu_mesh_vertices.py)
+lrhip_mesh_update_FLAGS = $(lrhip_instance_update_FLAGS)
 $(HIP_OBJ): $(OBJDIR)/%.o: $(HIPDIR)/%.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $($*_FLAGS) -c -o $@ $<

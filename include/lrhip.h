@@ -19,6 +19,7 @@
  *   lrhip_trace_rays               (no reference entry point: Geometry::trace_closest / trace_any for the caller's rays)
  *   lrhip_trace_radiance           (no reference entry point: MegakernelPathTracingInstance::Li for the caller's rays)
  *   lrhip_set_instance_transforms  (Geometry::update for matrices the caller holds, computed on the device)
+ *   lrhip_set_mesh_vertices        (no reference equivalent: new vertex positions for one mesh, re-baked and refitted on the device)
  *   lrhip_get_counters             (no reference equivalent; roofline accounting)
  *
  * Conventions: 0 = OK, negative = error (text via lrhip_last_error, thread-local); nothing
@@ -282,6 +283,55 @@ int lrhip_set_instance_transforms(lrhip_ctx *ctx, const lrhip_instance_update_pa
 /* HIP-event time of the kernels of the last lrhip_set_instance_transforms call, in ms; synchronises */
 double lrhip_last_instance_update_ms(lrhip_ctx *ctx);
 
+/* Deforming a mesh on the device (no reference equivalent: the reference's meshes are fixed after Geometry::build): new object-space
+ * vertex positions for one mesh of the uploaded scene -- a skinned character, cloth, a morph target, the output of an optimiser or a physics
+ * step that is a tensor on the GPU -- between two renders or queries, without parsing and uploading the scene again.
+ *   What it rewrites  vertices [first_vertex, first_vertex + count) of mesh `mesh` in the device vertex table get new px py pz, with `normals`
+ *                     also new nx ny nz; u v stay.  Then the baked BVH triangles and shading records of EVERY instance of that mesh (a mesh
+ *                     that several instances share, the Sphere shapes of one subdivision level for example, moves in all of them) and every
+ *                     BVH packet, refitted over the same topology and quantised again.  Afterwards the four tables lrhip_update_scene
+ *                     rewrites hold, byte for byte, what lrhip_update_scene would have written for the uploaded scene with these vertices
+ *                     in lr_scene.vertices, re-baked and refitted by the host (lrhost_scene_set_mesh_vertices), and the device vertex table
+ *                     holds the host's bytes.  Instance records, film, AOV buffers, counters, camera, environment, textures and the selected
+ *                     kernels stay.  The call is ordered on the context's stream behind earlier renders and queries and before later ones.
+ *   Normals           normals != NULL: written as given, not normalised.  normals == NULL without LRHIP_MESH_RECOMPUTE_NORMALS: kept -- the
+ *                     caller's choice for small deformations.  LRHIP_MESH_RECOMPUTE_NORMALS (normals must be NULL): the normals of ALL
+ *                     vertices of the mesh are recomputed from the new positions, area-weighted and deterministic.  For vertex v: s = (0,0,0);
+ *                     for every triangle t of the mesh in ascending t, and within it every corner in ascending order that names v,
+ *                     s += c_t = cross(p[i1] - p[i0], p[i2] - p[i0]) (components a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x);
+ *                     l2 = (s.x s.x + s.y s.y) + s.z s.z; if l2 > 0 && l2 <= FLT_MAX then n = s / sqrtf(l2) per component, otherwise the
+ *                     normal stays.  All of it fp32, unfused, with correctly rounded divide and sqrt.  Normals are written whether or not the
+ *                     mesh's instances carry LR_SHAPE_HAS_VERTEX_NORMAL; shading reads them only where the flag is set.  The first
+ *                     recomputing call on a mesh builds the mesh's corner lists from a read-back of its index range and SYNCHRONISES; the
+ *                     lists (12 B per mesh triangle + 4 B per vertex) stay with the context until the scene is released.
+ *   Emitters          a mesh of which any instance carries LR_SHAPE_HAS_LIGHT is refused with LRHIP_ERROR_UNSUPPORTED, nothing changed: the
+ *                     mesh's area alias table (tri_alias, tri_pdf) and the copy of tri_pdf in the shading records are functions of the
+ *                     object-space areas, and rebuilding them to the host's fp64-summed bits is a separate piece of work.
+ *   Pointers          without LRHIP_RAY_DEVICE_POINTERS both arrays are host memory: mesh < mesh_count, the range inside the mesh and every
+ *                     element finite are checked (else LRHIP_ERROR_INVALID, nothing changed), the arrays are staged through a context-owned
+ *                     buffer, and the call synchronises.  With it both are device memory, 4-byte aligned (else LRHIP_ERROR_INVALID), read in
+ *                     place, and the call is asynchronous on the context's stream; mesh and range are checked all the same (they are
+ *                     scalars), and non-finite values give non-finite tables -- the caller's error, but no fault and no endless loop.
+ *   The host scene    the caller's lr_scene is not read and does not change.  A later lrhip_update_scene (which copies lr_scene.vertices too)
+ *                     or lrhip_upload_scene overwrites what this call wrote: the host's tables win again.
+ *   Errors            LRHIP_ERROR_INVALID before any upload, for NULL positions with count > 0, normals together with
+ *                     LRHIP_MESH_RECOMPUTE_NORMALS, and unknown flags; LRHIP_ERROR_UNSUPPORTED for an emitter and for a BVH whose nodes are
+ *                     not stored parents first (as lrhip_set_instance_transforms).
+ *   Not done          emissive meshes; changing vertex or triangle counts or the topology; a BVH rebuild when a deformation degrades the
+ *                     tree (the refit keeps the build's topology); several meshes in one call; changing u v.                              */
+typedef struct lrhip_mesh_update_params {
+    const void *positions;   /* float[count][3], packed, object space */
+    const void *normals;     /* float[count][3], packed, or NULL */
+    uint32_t mesh;           /* index into lr_scene.meshes (lr_instance.handle.x >> 10) */
+    uint32_t first_vertex;   /* within the mesh */
+    uint64_t count;          /* 0 is legal and launches nothing */
+    uint32_t flags;          /* LRHIP_RAY_DEVICE_POINTERS, LRHIP_MESH_RECOMPUTE_NORMALS */
+} lrhip_mesh_update_params;
+#define LRHIP_MESH_RECOMPUTE_NORMALS 16u
+int lrhip_set_mesh_vertices(lrhip_ctx *ctx, const lrhip_mesh_update_params *params);
+/* HIP-event time of the kernels of the last lrhip_set_mesh_vertices call, in ms; synchronises */
+double lrhip_last_mesh_update_ms(lrhip_ctx *ctx);
+
 /* The path's only collective: sum-reduce of the per-rank films to rank `root` over RCCL / xGMI, in place on the film
  * this context accumulates into, in stream order behind the renders.  `nccl_comm` is the caller's ncclComm_t (one per process /
  * GPU, created by the caller: ncclCommInitRank); librccl.so is loaded on first use, so the library has no link-time dependency
@@ -428,13 +478,16 @@ int lrhip_plan_kernels(uint32_t features, uint32_t force_features, uint32_t flag
                        uint32_t out[LRHIP_PLAN_WORDS]);
 
 /* TEST HOOK (the product path never calls it): `bytes` bytes from `byte_offset` of one of the four device tables that move with the geometry,
- * as lrhip_upload_scene / lrhip_update_scene / lrhip_set_instance_transforms left them, copied to `out`.  Synchronises.  The tables: the
- * 64-byte BVH packets; the 48-byte baked triangles and, behind the last one, the all-zero sentinel the empty node slots name; the 128-byte
- * instance records; the 128-byte shading records.  LRHIP_ERROR_INVALID before any upload and for a range that is not inside the table.    */
+ * as lrhip_upload_scene / lrhip_update_scene / lrhip_set_instance_transforms / lrhip_set_mesh_vertices left them, copied to `out`.
+ * Synchronises.  The tables: the 64-byte BVH packets; the 48-byte baked triangles and, behind the last one, the all-zero sentinel the empty
+ * node slots name; the 128-byte instance records; the 128-byte shading records; and, as table 8, the object-space vertex table of 32-byte
+ * lr_vertex records that lrhip_set_mesh_vertices writes (ids 4 to 7 name no table).  LRHIP_ERROR_INVALID before any upload, for an unknown
+ * table and for a range that is not inside the table.                                                                                  */
 #define LRHIP_TABLE_NODES 0u
 #define LRHIP_TABLE_BVH_TRIANGLES 1u
 #define LRHIP_TABLE_INSTANCES 2u
 #define LRHIP_TABLE_SHADE_TRIANGLES 3u
+#define LRHIP_TABLE_VERTICES 8u
 int lrhip_read_scene_table(lrhip_ctx *ctx, uint32_t which, uint64_t byte_offset, uint64_t bytes, void *out);
 /* size in bytes of that table in the uploaded scene (0: none, or an unknown table) */
 uint64_t lrhip_scene_table_bytes(lrhip_ctx *ctx, uint32_t which);

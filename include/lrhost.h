@@ -49,6 +49,16 @@ int lrhost_scene_set_time(lrhost_scene *scene, float time, int *updated);
  * twice, a non-finite matrix element, or NULL matrices with count > 0.  A later lrhost_scene_set_time moves the instances that carry
  * an animated transform to their transform's value again; the others keep what this call gave them.                              */
 int lrhost_scene_set_instance_transforms(lrhost_scene *scene, uint64_t count, const uint32_t *instances, const float *object_to_world);
+/* Deforming a mesh (the host mirror of lrhip.h's lrhip_set_mesh_vertices, which has the semantics): vertices [first_vertex, first_vertex + count)
+ * of mesh `mesh` get positions[i] (float[3], packed, object space) and, when `normals` is not NULL, normals[i]; u v stay.  flags: 0 or
+ * LRHIP_MESH_RECOMPUTE_NORMALS (normals must be NULL then), which recomputes the normals of all vertices of the mesh by lrhip.h's
+ * definition, as a plain sequential loop.  The baked triangles of every instance of the mesh are re-baked and the BVH is refitted over the
+ * same topology when it is built; the tables behind lrhost_scene_view change in place (lrhip_update_scene, or upload the scene again).
+ * An error, with nothing changed, for a mesh or a range out of bounds, a non-finite element, NULL positions with count > 0, normals
+ * together with the flag, unknown flags, and for a mesh of which an instance carries a light: tri_alias and tri_pdf are not rebuilt.
+ * A later lrhost_scene_set_time re-bakes animated instances from the new vertices.                                                      */
+int lrhost_scene_set_mesh_vertices(lrhost_scene *scene, uint32_t mesh, uint32_t first_vertex, uint64_t count, const float *positions,
+                                   const float *normals, uint32_t flags);
 int lrhost_scene_shutter_sample_count(const lrhost_scene *scene, int camera_index);
 int lrhost_scene_shutter_sample(const lrhost_scene *scene, int camera_index, int sample_index, float *time, float *weight, uint32_t *spp);
 int lrhost_scene_camera_count(const lrhost_scene *scene);

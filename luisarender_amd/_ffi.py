@@ -162,17 +162,24 @@ class InstanceUpdateParams(C.Structure):
     _fields_ = [("object_to_world", C.c_void_p), ("instances", C.c_void_p), ("count", u64), ("flags", u32)]
 
 
-# lrhip_read_scene_table's tables (LRHIP_TABLE_*) and the bytes of one record of each
-TABLE_NODES, TABLE_BVH_TRIANGLES, TABLE_INSTANCES, TABLE_SHADE_TRIANGLES = 0, 1, 2, 3
-TABLE_RECORD_BYTES = (64, 48, 128, 128)
+class MeshUpdateParams(C.Structure):
+    """lrhip_mesh_update_params (include/lrhip.h)"""
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("mesh", u32), ("first_vertex", u32), ("count", u64), ("flags", u32)]
+
+
+# lrhip_read_scene_table's tables (LRHIP_TABLE_*) and the bytes of one record of each (ids 4 to 7 name no table)
+TABLE_NODES, TABLE_BVH_TRIANGLES, TABLE_INSTANCES, TABLE_SHADE_TRIANGLES, TABLE_VERTICES = 0, 1, 2, 3, 8
+TABLE_RECORD_BYTES = {TABLE_NODES: 64, TABLE_BVH_TRIANGLES: 48, TABLE_INSTANCES: 128, TABLE_SHADE_TRIANGLES: 128, TABLE_VERTICES: 32}
 
 RAY_CLOSEST, RAY_ANY = 0, 1  # LRHIP_RAY_CLOSEST / LRHIP_RAY_ANY
 RAY_DEVICE_POINTERS, RAY_ALPHA_TEST = 1, 2  # LRHIP_RAY_DEVICE_POINTERS / LRHIP_RAY_ALPHA_TEST
 RADIANCE_ACCUMULATE, RADIANCE_COUNTERS = 4, 8  # LRHIP_RADIANCE_ACCUMULATE / LRHIP_RADIANCE_COUNTERS
 FEAT_QUERY = 65536  # LRHIP_FEAT_QUERY
+MESH_RECOMPUTE_NORMALS = 16  # LRHIP_MESH_RECOMPUTE_NORMALS
 
 STRUCTS = {"lrhip_denoise_params": DenoiseParams, "lrhip_ray": Ray, "lrhip_ray_hit": RayHit, "lrhip_ray_query_params": RayQueryParams,
            "lrhip_radiance_query_params": RadianceQueryParams, "lrhip_instance_update_params": InstanceUpdateParams,
+           "lrhip_mesh_update_params": MeshUpdateParams,
            "lr_scene": Scene, "lr_vertex": Vertex, "lr_triangle": Triangle, "lr_alias_entry": AliasEntry,
            "lr_mesh": Mesh, "lr_instance": Instance, "lr_texture": Texture, "lr_surface": Surface,
            "lr_light": Light, "lr_environment": Environment, "lr_camera": Camera, "lr_filter": Filter,
@@ -219,6 +226,7 @@ def host_lib() -> C.CDLL:
         lib.lrhost_scene_build_accel.argtypes = [C.c_void_p]
         lib.lrhost_scene_set_time.argtypes = [C.c_void_p, f32, C.POINTER(C.c_int)]
         lib.lrhost_scene_set_instance_transforms.argtypes = [C.c_void_p, u64, C.c_void_p, C.c_void_p]
+        lib.lrhost_scene_set_mesh_vertices.argtypes = [C.c_void_p, u32, u32, u64, C.c_void_p, C.c_void_p, u32]
         lib.lrhost_scene_shutter_sample_count.argtypes = [C.c_void_p, C.c_int]
         lib.lrhost_scene_shutter_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(f32), C.POINTER(f32), C.POINTER(u32)]
         lib.lrhost_scene_camera_count.argtypes = [C.c_void_p]
@@ -292,6 +300,9 @@ def hip_lib(path: str | None = None) -> C.CDLL:
         lib.lrhip_set_instance_transforms.argtypes = [C.c_void_p, C.POINTER(InstanceUpdateParams)]
         lib.lrhip_last_instance_update_ms.restype = C.c_double
         lib.lrhip_last_instance_update_ms.argtypes = [C.c_void_p]
+        lib.lrhip_set_mesh_vertices.argtypes = [C.c_void_p, C.POINTER(MeshUpdateParams)]
+        lib.lrhip_last_mesh_update_ms.restype = C.c_double
+        lib.lrhip_last_mesh_update_ms.argtypes = [C.c_void_p]
         lib.lrhip_read_scene_table.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
         lib.lrhip_scene_table_bytes.restype = C.c_uint64
         lib.lrhip_scene_table_bytes.argtypes = [C.c_void_p, C.c_uint32]

@@ -1,7 +1,8 @@
 // lrhip_instance_update.hip — C ABI of moving instances on the device (include/lrhip.h: lrhip_set_instance_transforms,
 // lrhip_last_instance_update_ms) and the test hook that reads the moved tables back (lrhip_read_scene_table).  Holds the kernels
-// of instance_update_kernels.h.  This object is held to unfused host code bit for bit, so it is built with flags of its own: no fp
-// contraction, correctly rounded fp32 division (Makefile: lrhip_instance_update_FLAGS).
+// of instance_update_kernels.h, and launches the re-bake and refit for lrhip_mesh_update.hip too (rebake_and_refit).  This object is held
+// to unfused host code bit for bit, so it is built with flags of its own: no fp contraction, correctly rounded fp32 division (Makefile:
+// lrhip_instance_update_FLAGS).
 #include "lrhip_internal.h"
 #include "instance_update_kernels.h"
 
@@ -26,24 +27,18 @@ size_t table_bytes(const lrhip_ctx *ctx, uint32_t which, const void **base) {
         case LRHIP_TABLE_BVH_TRIANGLES: *base = d.bvh_tris; return (static_cast<size_t>(ctx->update_counts[1]) + 1u) * sizeof(lr_bvh_triangle);
         case LRHIP_TABLE_INSTANCES: *base = d.instances; return static_cast<size_t>(ctx->update_counts[2]) * sizeof(lrd::DInstance);
         case LRHIP_TABLE_SHADE_TRIANGLES: *base = d.shade_tris; return static_cast<size_t>(ctx->update_counts[1]) * sizeof(lrd::DShadeTri);
+        case LRHIP_TABLE_VERTICES: *base = d.vertices; return static_cast<size_t>(ctx->vertex_count) * sizeof(lr_vertex);
         default: return 0u;
     }
 }
 
 unsigned blocks_for(uint64_t threads) { return static_cast<unsigned>((threads + lrd::kUpdateBlock - 1u) / lrd::kUpdateBlock); }
 
-// the kernels of one call over `count` matrices in device memory, between the context's update events
-int update_device(lrhip_ctx *ctx, const void *matrices, const void *ids, uint32_t count) {
+// the tables of the uploaded scene as the kernels take them, with the call's scratch
+lrd::InstanceUpdateArgs scene_args(lrhip_ctx *ctx) {
     const auto &d = ctx->scene;
     const auto instance_count = ctx->update_counts[2];
-    if (instance_count == 0u) { return LRHIP_OK; }// (every id is out of range)
-    // scratch of the call: an owner word per instance, then a bit per instance; cleared per call, so that nothing leaks from the call before
-    const auto owner_bytes = static_cast<size_t>(instance_count) * sizeof(uint32_t);
-    const auto mask_bytes = (static_cast<size_t>(instance_count) + 31u) / 32u * sizeof(uint32_t);
-    if (auto r = ensure(ctx->update_scratch, owner_bytes + mask_bytes); r != LRHIP_OK) { return r; }
-    LR_HIP_CHECK(hipMemsetAsync(ctx->update_scratch.ptr, 0, owner_bytes + mask_bytes, ctx->stream));
     lrd::InstanceUpdateArgs a{};
-    a.matrices = static_cast<const float4 *>(matrices), a.ids = static_cast<const uint32_t *>(ids), a.count = count;
     a.instances = const_cast<lrd::DInstance *>(d.instances), a.instance_count = instance_count;
     a.bvh_tris = const_cast<lr_bvh_triangle *>(d.bvh_tris), a.triangle_count = ctx->update_counts[1];
     a.shade_tris = const_cast<lrd::DShadeTri *>(d.shade_tris);
@@ -52,25 +47,23 @@ int update_device(lrhip_ctx *ctx, const void *matrices, const void *ids, uint32_
     a.vertices = d.vertices, a.vertex_count = static_cast<uint32_t>(std::min<uint64_t>(ctx->vertex_count, 0xffffffffull));
     a.triangles = d.triangles, a.mesh_triangle_count = ctx->update_counts[3];
     a.owner = static_cast<uint32_t *>(ctx->update_scratch.ptr);
-    a.moved = a.owner + instance_count;
+    a.moved = update_moved_mask(ctx);
+    return a;
+}
+
+// the kernels of one call over `count` matrices in device memory, between the context's update events
+int update_device(lrhip_ctx *ctx, const void *matrices, const void *ids, uint32_t count) {
+    if (ctx->update_counts[2] == 0u) { return LRHIP_OK; }// (every id is out of range)
+    if (auto r = clear_update_scratch(ctx); r != LRHIP_OK) { return r; }
+    auto a = scene_args(ctx);
+    a.matrices = static_cast<const float4 *>(matrices), a.ids = static_cast<const uint32_t *>(ids), a.count = count;
     const dim3 block(lrd::kUpdateBlock);
     LR_HIP_CHECK(hipEventRecord(ctx->update_begin, ctx->stream));
     hipLaunchKernelGGL(lrd::instance_claim_kernel, dim3(blocks_for(count)), block, 0, ctx->stream, a);
     LR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(lrd::instance_record_kernel, dim3(blocks_for(count)), block, 0, ctx->stream, a);
     LR_HIP_CHECK(hipGetLastError());
-    if (a.triangle_count != 0u) {
-        hipLaunchKernelGGL(lrd::instance_triangle_kernel, dim3(blocks_for(a.triangle_count)), block, 0, ctx->stream, a);
-        LR_HIP_CHECK(hipGetLastError());
-    }
-    // every node of every level, from the deepest level up (restricting the refit to the ancestors of moved triangles: not done)
-    for (auto l = ctx->level_offsets.size() - 1u; l-- > 0u;) {
-        const auto first = ctx->level_offsets[l], n = ctx->level_offsets[l + 1u] - first;
-        if (n == 0u) { continue; }
-        hipLaunchKernelGGL(lrd::instance_refit_kernel, dim3(blocks_for(static_cast<uint64_t>(n) * 4u)), block, 0, ctx->stream, a,
-                           ctx->level_nodes + first, n);
-        LR_HIP_CHECK(hipGetLastError());
-    }
+    if (auto r = rebake_and_refit(ctx); r != LRHIP_OK) { return r; }
     LR_HIP_CHECK(hipEventRecord(ctx->update_end, ctx->stream));
     ctx->update_pending = true;
     return LRHIP_OK;
@@ -87,6 +80,36 @@ int collect_time(lrhip_ctx *ctx) {
 }
 
 }// namespace
+
+// scratch of a call: an owner word per instance, then a bit per instance; cleared per call, so that nothing leaks from the call before
+int clear_update_scratch(lrhip_ctx *ctx) {
+    const auto instance_count = ctx->update_counts[2];
+    const auto owner_bytes = static_cast<size_t>(instance_count) * sizeof(uint32_t);
+    const auto mask_bytes = (static_cast<size_t>(instance_count) + 31u) / 32u * sizeof(uint32_t);
+    if (auto r = ensure(ctx->update_scratch, owner_bytes + mask_bytes); r != LRHIP_OK) { return r; }
+    if (owner_bytes + mask_bytes != 0u) { LR_HIP_CHECK(hipMemsetAsync(ctx->update_scratch.ptr, 0, owner_bytes + mask_bytes, ctx->stream)); }
+    return LRHIP_OK;
+}
+
+uint32_t *update_moved_mask(lrhip_ctx *ctx) { return static_cast<uint32_t *>(ctx->update_scratch.ptr) + ctx->update_counts[2]; }
+
+int rebake_and_refit(lrhip_ctx *ctx) {
+    const auto a = scene_args(ctx);
+    const dim3 block(lrd::kUpdateBlock);
+    if (a.triangle_count != 0u) {
+        hipLaunchKernelGGL(lrd::instance_triangle_kernel, dim3(blocks_for(a.triangle_count)), block, 0, ctx->stream, a);
+        LR_HIP_CHECK(hipGetLastError());
+    }
+    // every node of every level, from the deepest level up (restricting the refit to the ancestors of moved triangles: not done)
+    for (auto l = ctx->level_offsets.size() - 1u; l-- > 0u;) {
+        const auto first = ctx->level_offsets[l], n = ctx->level_offsets[l + 1u] - first;
+        if (n == 0u) { continue; }
+        hipLaunchKernelGGL(lrd::instance_refit_kernel, dim3(blocks_for(static_cast<uint64_t>(n) * 4u)), block, 0, ctx->stream, a,
+                           ctx->level_nodes + first, n);
+        LR_HIP_CHECK(hipGetLastError());
+    }
+    return LRHIP_OK;
+}
 
 }// namespace lrh
 
@@ -166,7 +189,7 @@ uint64_t lrhip_scene_table_bytes(lrhip_ctx *ctx, uint32_t which) {
 
 int lrhip_read_scene_table(lrhip_ctx *ctx, uint32_t which, uint64_t byte_offset, uint64_t bytes, void *out) {
     if (ctx == nullptr || !ctx->scene_ready) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: no scene uploaded"); }
-    if (which > LRHIP_TABLE_SHADE_TRIANGLES) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: unknown table"); }
+    if (which > LRHIP_TABLE_SHADE_TRIANGLES && which != LRHIP_TABLE_VERTICES) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: unknown table"); }
     const void *base = nullptr;
     const auto size = table_bytes(ctx, which, &base);
     if (byte_offset > size || bytes > size - byte_offset) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: the range is not inside the table"); }

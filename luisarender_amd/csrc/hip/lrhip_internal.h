@@ -11,6 +11,7 @@
 //   lrhip_raycast.hip    ray queries: closest hit / occlusion for caller-supplied rays (raycast_kernel.h)
 //   lrhip_radiance.hip   radiance queries: MegaPath's estimator along caller-supplied rays (the kFeatQuery kernels of megapath_kernel.h)
 //   lrhip_instance_update.hip  moving instances on the device: re-bake, refit and re-quantise (instance_update_kernels.h); the table test hook
+//   lrhip_mesh_update.hip      deforming a mesh on the device: vertex write, normal recompute, marking (mesh_update_kernels.h), then the re-bake and refit
 // Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
 #pragma once
 #include "../../../include/lrhip.h"
@@ -189,6 +190,16 @@ struct lrhip_ctx {
     hipEvent_t update_begin{nullptr}, update_end{nullptr};
     double update_ms{0.};
     bool update_pending{false};
+    // deforming a mesh (lrhip_mesh_update.hip).  Of the uploaded scene: a host copy of the lr_mesh table, per mesh the first instance that
+    // carries a light (LR_INVALID_ID: none -- an emitter's vertices are not moved), and per mesh the corner lists of the normal recompute in
+    // device memory, built on first use and released with the scene.  Of the context: the events around the last call's kernels and its
+    // kernel time once read (lrhip_last_mesh_update_ms).  Staging buffer and scratch are the instance call's
+    std::vector<lr_mesh> meshes;
+    std::vector<uint32_t> mesh_light;
+    std::vector<lrh::DeviceBuffer> mesh_adjacency;
+    hipEvent_t mesh_begin{nullptr}, mesh_end{nullptr};
+    double mesh_ms{0.};
+    bool mesh_pending{false};
 };
 
 namespace lrh {
@@ -230,5 +241,14 @@ hipError_t launch_wf_resolve(lrhip_ctx *ctx, double inv_scale);
 // resolve_partial_kernel over a "frame" of `count` records instead of the film's pixels (radiance queries): records[i] += sum of partial[c][i]
 hipError_t launch_resolve_records(lrhip_ctx *ctx, float4 *records, const float4 *partial, uint32_t count, uint32_t chunk_count);
 hipError_t launch_wf_carry(lrhip_ctx *ctx, uint32_t margin, uint32_t mode);
+
+// lrhip_instance_update.hip, for the calls that move geometry on the device (the __global__ functions of instance_update_kernels.h live in
+// that object).  The call's scratch is an owner word per instance, then a bit per instance.  clear_update_scratch: sizes it for the uploaded
+// scene and clears it on the context's stream.  update_moved_mask: its bit per instance, valid after clear_update_scratch.
+// rebake_and_refit: instance_triangle_kernel over the instances whose bit is set, then instance_refit_kernel level by level from the
+// deepest up, on the context's stream
+int clear_update_scratch(lrhip_ctx *ctx);
+uint32_t *update_moved_mask(lrhip_ctx *ctx);
+int rebake_and_refit(lrhip_ctx *ctx);
 
 }// namespace lrh

@@ -371,6 +371,16 @@ int upload_refit_tables(lrhip_ctx *ctx, const lr_scene *s) {
     LR_UP(upload(ctx, s->accel.nodes, s->accel.node_count, &nodes32));
     ctx->nodes32 = const_cast<lr_bvh4_node *>(nodes32);
     ctx->vertex_count = s->vertex_count;
+    // what lrhip_set_mesh_vertices checks its argument against (lrhip_mesh_update.hip): the mesh table, and which meshes emit
+    ctx->meshes.assign(s->meshes, s->meshes + s->mesh_count);
+    ctx->mesh_light.assign(s->mesh_count, LR_INVALID_ID);
+    ctx->mesh_adjacency.assign(s->mesh_count, DeviceBuffer{});
+    for (uint32_t i = 0u; i < s->instance_count; i++) {
+        const auto handle = s->instances[i].handle.x;
+        if ((handle & LR_SHAPE_HAS_LIGHT) != 0u && (handle >> 10u) < s->mesh_count && ctx->mesh_light[handle >> 10u] == LR_INVALID_ID) {
+            ctx->mesh_light[handle >> 10u] = i;
+        }
+    }
     const auto n = s->accel.node_count;
     std::vector<uint32_t> level(n, 0u);
     auto depth = 0u;
@@ -538,8 +548,8 @@ int lrhip_update_scene(lrhip_ctx *ctx, const lr_scene *s) {
     // 256 shutter samples must not push its textures and environment tables through PCIe 256 times.  Everything else must be
     // the scene that was uploaded; the table sizes are the part of that contract that can be checked.
     if (s->accel.nodes == nullptr || s->accel.node_count != ctx->update_counts[0] || s->accel.triangle_count != ctx->update_counts[1] ||
-        s->instance_count != ctx->update_counts[2] || s->triangle_count != ctx->update_counts[3] || s->texture_count != ctx->update_counts[4] ||
-        s->surface_count != ctx->update_counts[5] || s->environment.kind != ctx->update_counts[6]) {
+        s->instance_count != ctx->update_counts[2] || s->triangle_count != ctx->update_counts[3] || s->vertex_count != ctx->vertex_count ||
+        s->texture_count != ctx->update_counts[4] || s->surface_count != ctx->update_counts[5] || s->environment.kind != ctx->update_counts[6]) {
         return fail(LRHIP_ERROR_INVALID,
             "lrhip_update_scene: not the uploaded scene at another time (table sizes differ); use lrhip_upload_scene");
     }
@@ -563,6 +573,8 @@ int lrhip_update_scene(lrhip_ctx *ctx, const lr_scene *s) {
     LR_HIP_CHECK(copy(d.shade_tris, shade.data(), shade.size() * sizeof(shade[0])));
     // the fp32 boxes a later lrhip_set_instance_transforms refits from: the host's tables win again
     LR_HIP_CHECK(copy(ctx->nodes32, s->accel.nodes, static_cast<size_t>(s->accel.node_count) * sizeof(lr_bvh4_node)));
+    // ... and the object-space vertices it, and lrhip_set_mesh_vertices, re-bake from: either side may have deformed a mesh since
+    LR_HIP_CHECK(copy(d.vertices, s->vertices, static_cast<size_t>(s->vertex_count) * sizeof(lr_vertex)));
     LR_HIP_CHECK(hipStreamSynchronize(ctx->stream));// the host vectors above go out of scope
     set_camera(d, s);
     if (d.env_kind == lrd::kEnvConstant) {

@@ -86,6 +86,14 @@ int lrhost_scene_set_instance_transforms(lrhost_scene *scene, uint64_t count, co
     });
 }
 
+int lrhost_scene_set_mesh_vertices(lrhost_scene *scene, uint32_t mesh, uint32_t first_vertex, uint64_t count, const float *positions,
+                                   const float *normals, uint32_t flags) {
+    return guarded([&] {
+        if (scene == nullptr) { throw lr::Error{"Mesh vertices: the scene is NULL."}; }
+        lr::set_scene_mesh_vertices(*scene->data, mesh, first_vertex, count, positions, normals, flags);
+    });
+}
+
 int lrhost_scene_shutter_sample_count(const lrhost_scene *scene, int camera_index) {
     if (camera_index < 0 || static_cast<size_t>(camera_index) >= scene->data->cameras.size()) { return 0; }
     return static_cast<int>(scene->data->cameras[static_cast<size_t>(camera_index)].shutter_samples.size());
@@ -165,7 +173,7 @@ uint64_t lrhost_sizeof(const char *name) {
     LR_SIZEOF(lr_bvh4_node) LR_SIZEOF(lr_bvh_triangle) LR_SIZEOF(lr_accel) LR_SIZEOF(lr_light_handle)
     LR_SIZEOF(lr_medium) LR_SIZEOF(lrhip_denoise_params)
     LR_SIZEOF(lrhip_ray) LR_SIZEOF(lrhip_ray_hit) LR_SIZEOF(lrhip_ray_query_params) LR_SIZEOF(lrhip_radiance_query_params)
-    LR_SIZEOF(lrhip_instance_update_params)
+    LR_SIZEOF(lrhip_instance_update_params) LR_SIZEOF(lrhip_mesh_update_params)
 #undef LR_SIZEOF
     return 0u;
 }

@@ -1740,6 +1740,71 @@ void set_scene_instance_transforms(SceneData &scene, uint64_t count, const uint3
     if (!scene.bvh_nodes.empty()) { refit_accel(scene, moved); }
 }
 
+void set_scene_mesh_vertices(SceneData &scene, uint32_t mesh_id, uint32_t first, uint64_t count, const float *positions, const float *normals,
+                             uint32_t flags) {
+    if ((flags & ~LRHIP_MESH_RECOMPUTE_NORMALS) != 0u) { throw Error{"Mesh vertices: unknown flags."}; }
+    if (mesh_id >= scene.meshes.size()) {
+        throw Error{"Mesh vertices: mesh " + std::to_string(mesh_id) + " out of range (" + std::to_string(scene.meshes.size()) + " meshes)."};
+    }
+    const auto mesh = scene.meshes[mesh_id];
+    if (first > mesh.vertex_count || count > mesh.vertex_count - first) {
+        throw Error{"Mesh vertices: vertices " + std::to_string(first) + " + " + std::to_string(count) + " are not inside the mesh's " +
+                    std::to_string(mesh.vertex_count) + "."};
+    }
+    if (count != 0u && positions == nullptr) { throw Error{"Mesh vertices: the positions are NULL."}; }
+    const auto recompute = (flags & LRHIP_MESH_RECOMPUTE_NORMALS) != 0u;
+    if (recompute && normals != nullptr) { throw Error{"Mesh vertices: normals must be NULL with LRHIP_MESH_RECOMPUTE_NORMALS."}; }
+    std::vector<char> moved(scene.instances.size(), 0);
+    for (size_t i = 0u; i < scene.instances.size(); i++) {
+        if ((scene.instances[i].handle.x >> 10u) != mesh_id) { continue; }
+        if ((scene.instances[i].handle.x & LR_SHAPE_HAS_LIGHT) != 0u) {
+            throw Error{"Mesh vertices: mesh " + std::to_string(mesh_id) + " is an emitter (instance " + std::to_string(i) +
+                        " carries a light): its area sampling tables are not rebuilt."};
+        }
+        moved[i] = 1;
+    }
+    for (auto array : {positions, normals}) {
+        for (uint64_t i = 0u; array != nullptr && i < count * 3u; i++) {
+            if (!std::isfinite(array[i])) {
+                throw Error{"Mesh vertices: vertex " + std::to_string(i / 3u) + " has a non-finite " + (array == normals ? "normal." : "position.")};
+            }
+        }
+    }
+    if (count == 0u) { return; }
+    const auto vertices = scene.vertices.data() + mesh.vertex_offset;
+    for (uint64_t i = 0u; i < count; i++) {
+        auto &v = vertices[first + i];
+        v.px = positions[i * 3u], v.py = positions[i * 3u + 1u], v.pz = positions[i * 3u + 2u];
+        if (normals != nullptr) { v.nx = normals[i * 3u], v.ny = normals[i * 3u + 1u], v.nz = normals[i * 3u + 2u]; }
+    }
+    if (recompute) {
+        // lrhip.h's definition: the sums in ascending triangle, then ascending corner order; unfused fp32 (the host objects are built without FMA)
+        std::vector<float3> sum(mesh.vertex_count, float3{0.f, 0.f, 0.f});
+        for (uint32_t t = 0u; t < mesh.triangle_count; t++) {
+            const auto tri = scene.triangles[mesh.triangle_offset + t];
+            const uint32_t index[3] = {tri.i0, tri.i1, tri.i2};
+            if (index[0] >= mesh.vertex_count || index[1] >= mesh.vertex_count || index[2] >= mesh.vertex_count) { continue; }
+            const auto &p0 = vertices[index[0]], &p1 = vertices[index[1]], &p2 = vertices[index[2]];
+            const float a[3] = {p1.px - p0.px, p1.py - p0.py, p1.pz - p0.pz};
+            const float b[3] = {p2.px - p0.px, p2.py - p0.py, p2.pz - p0.pz};
+            const float c[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+            for (auto k : index) {
+                auto &s = sum[k];
+                s.x = s.x + c[0], s.y = s.y + c[1], s.z = s.z + c[2];
+            }
+        }
+        for (uint32_t i = 0u; i < mesh.vertex_count; i++) {
+            const auto s = sum[i];
+            const auto l2 = (s.x * s.x + s.y * s.y) + s.z * s.z;
+            if (l2 > 0.f && l2 <= std::numeric_limits<float>::max()) {
+                const auto l = std::sqrt(l2);
+                vertices[i].nx = s.x / l, vertices[i].ny = s.y / l, vertices[i].nz = s.z / l;
+            }
+        }
+    }
+    if (!scene.bvh_nodes.empty()) { refit_accel(scene, moved); }
+}
+
 std::unique_ptr<SceneData> build_scene(const SceneDesc &desc) {
     auto out = std::make_unique<SceneData>();
     Builder{desc, *out}.build();

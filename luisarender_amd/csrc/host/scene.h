@@ -130,6 +130,13 @@ bool set_scene_time(SceneData &scene, float time);
 // matrices[i] (column-major, the layout of lr_instance.object_to_world), and the BVH is refitted for these instances if it is built.  Throws
 // on an id out of range or listed twice, a non-finite element, or more matrices than instances without ids; nothing has changed then
 void set_scene_instance_transforms(SceneData &scene, uint64_t count, const uint32_t *ids, const float *matrices);
+// scene.cpp: the host mirror of lrhip_set_mesh_vertices (lrhip.h has the semantics and the definition of the normal recompute): writes
+// positions (and normals) of vertices [first, first + count) of mesh `mesh`, recomputes the mesh's normals with LRHIP_MESH_RECOMPUTE_NORMALS,
+// and refits the BVH for the mesh's instances if it is built; tri_alias and tri_pdf are not touched.  Throws on a mesh or range out of bounds,
+// a non-finite element, NULL positions, normals with the flag, unknown flags and an emitter mesh; nothing has changed then.  The expressions
+// of the recompute are the device's (csrc/hip/mesh_update_kernels.h: mesh_normal_kernel): change them only together
+void set_scene_mesh_vertices(SceneData &scene, uint32_t mesh, uint32_t first, uint64_t count, const float *positions, const float *normals,
+                             uint32_t flags);
 
 // mesh_io.cpp: OBJ loader standing in for assimp (src/shapes/mesh.cpp:46-69 flag semantics)
 struct LoadedMesh {

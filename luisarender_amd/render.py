@@ -160,6 +160,55 @@ def check_instance_transforms(matrices, instances=None, instance_count: int | No
     return kind
 
 
+def check_mesh_vertices(positions, normals=None, mesh: int = 0, first: int = 0, meshes=None, device: int | None = None) -> str:
+    """What MegaPathRenderer.set_mesh_vertices and Scene.set_mesh_vertices accept (no device needed).  positions: float32, contiguous,
+    [N, 3], object space; normals: None or an array of the same kind, dtype and shape.  mesh, first: the mesh (an index into
+    lr_scene.meshes) and the first vertex within it; meshes: the vertex count of every mesh of the scene (None: no range checks).  numpy
+    arrays -> "numpy": every element finite.  torch tensors on GPU `device` (None: any GPU) -> "torch": values on the device are not looked
+    at.  ValueError for anything else."""
+    what = "set_mesh_vertices"
+
+    def kind_of(array, name):
+        if isinstance(array, np.ndarray):
+            kind, contiguous, is_float32 = "numpy", array.flags["C_CONTIGUOUS"], array.dtype == np.float32
+        elif type(array).__module__.split(".")[0] == "torch" and hasattr(array, "data_ptr"):
+            import torch
+            kind, contiguous, is_float32 = "torch", array.is_contiguous(), array.dtype == torch.float32
+            if array.device.type != "cuda":
+                raise ValueError(f"{what}: the {name} tensor is on {array.device}, not on a GPU")
+            if device is not None and array.device.index != device:
+                raise ValueError(f"{what}: the {name} tensor is on {array.device}, the renderer on GPU {device}")
+        else:
+            raise ValueError(f"{what}: {name} must be a numpy array or a torch tensor, not {type(array).__name__}")
+        if not is_float32:
+            raise ValueError(f"{what}: {name} must be float32, not {array.dtype}")
+        if len(array.shape) != 2 or array.shape[1] != 3:
+            raise ValueError(f"{what}: {name} must have shape [N, 3], not {tuple(array.shape)}")
+        if not contiguous:
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if kind == "numpy" and not np.isfinite(array).all():
+            raise ValueError(f"{what}: {name} has a non-finite element")
+        return kind
+
+    kind = kind_of(positions, "positions")
+    if normals is not None:
+        if kind_of(normals, "normals") != kind:
+            raise ValueError(f"{what}: positions and normals must both be numpy arrays or both torch tensors")
+        if tuple(normals.shape) != tuple(positions.shape):
+            raise ValueError(f"{what}: normals must have positions' shape {tuple(positions.shape)}, not {tuple(normals.shape)}")
+        if kind == "torch" and normals.device != positions.device:
+            raise ValueError(f"{what}: normals is on {normals.device}, positions on {positions.device}")
+    for name, value in (("mesh", mesh), ("first", first)):
+        if not isinstance(value, (int, np.integer)) or isinstance(value, bool) or not 0 <= int(value) <= 0xFFFFFFFF:
+            raise ValueError(f"{what}: {name} must be an integer in [0, 2^32), not {value!r}")
+    if meshes is not None:
+        if int(mesh) >= len(meshes):
+            raise ValueError(f"{what}: mesh {mesh} out of range ({len(meshes)} meshes)")
+        if int(first) + int(positions.shape[0]) > int(meshes[int(mesh)]):
+            raise ValueError(f"{what}: vertices {first} + {positions.shape[0]} are not inside the mesh's {int(meshes[int(mesh)])}")
+    return kind
+
+
 class RayHits:
     """Closest hits of MegaPathRenderer.trace: views (no copies) of ONE [N, 8] 32-bit buffer of lrhip_ray_hit records -- `buffer`, a
     float32 numpy array or, for the torch path, the float32 tensor on the device.  t (+inf: a miss), u, v: float32; inst, prim, tri:
@@ -415,9 +464,46 @@ class MegaPathRenderer:
         """lrhip_last_instance_update_ms: HIP-event time of the kernels of the last set_instance_transforms()"""
         return float(self._lib.lrhip_last_instance_update_ms(self._ctx))
 
+    def set_mesh_vertices(self, mesh: int, positions, normals=None, first: int = 0, recompute_normals: bool = False, sync: bool = True) -> None:
+        """lrhip_set_mesh_vertices (lrhip.h has the semantics): deform one mesh of the uploaded scene on the device -- vertices first ..
+        first + N - 1 of mesh `mesh` (Scene.instance_mesh gives an instance's) get the object-space positions [N, 3] and, if given, the
+        normals [N, 3]; the baked triangles and shading records of every instance of the mesh are rewritten and the BVH is refitted and
+        quantised again, in stream order behind earlier renders and queries; film, counters and everything else stay.  normals None: kept,
+        or with recompute_normals recomputed for the whole mesh from the new positions (area-weighted; the first such call on a mesh
+        synchronises).  A mesh with an emissive instance is refused.  float32 numpy arrays go through host pointers (checked, the call
+        synchronises).  torch tensors on this renderer's GPU are read in place and the call is asynchronous on the context's stream: torch's
+        current stream is synchronised before it; sync=False skips that for a caller who has bound the context to torch's stream
+        (set_stream).  The kernels read the tensors' memory when the stream reaches them, not when this method returns: keep the tensors
+        referenced and unmodified until the context's stream has passed the call (synchronize(), or any later call that synchronises).  A mesh or
+        range outside the uploaded scene is a DeviceError.  The host Scene is not touched: a later upload() of it, with or without
+        keep_film, brings the host's tables back; Scene.set_mesh_vertices keeps it in step."""
+        if recompute_normals and normals is not None:
+            raise ValueError("set_mesh_vertices: normals must be None with recompute_normals")
+        kind = check_mesh_vertices(positions, normals, mesh, first, None, self._device)  # mesh and range: the library checks them against the upload
+        p = _ffi.MeshUpdateParams()
+        p.mesh, p.first_vertex, p.count = int(mesh), int(first), int(positions.shape[0])
+        p.flags = _ffi.MESH_RECOMPUTE_NORMALS if recompute_normals else 0
+        if kind == "numpy":
+            p.positions = positions.ctypes.data
+            p.normals = normals.ctypes.data if normals is not None else None
+            self._check(self._lib.lrhip_set_mesh_vertices(self._ctx, C.byref(p)))
+            return
+        import torch
+        p.positions = positions.data_ptr()
+        p.normals = normals.data_ptr() if normals is not None else None
+        p.flags |= _ffi.RAY_DEVICE_POINTERS
+        if sync:
+            torch.cuda.current_stream(positions.device).synchronize()
+        self._check(self._lib.lrhip_set_mesh_vertices(self._ctx, C.byref(p)))
+
+    def last_mesh_update_ms(self) -> float:
+        """lrhip_last_mesh_update_ms: HIP-event time of the kernels of the last set_mesh_vertices()"""
+        return float(self._lib.lrhip_last_mesh_update_ms(self._ctx))
+
     def scene_table(self, which: int) -> np.ndarray:
         """tests / tools only (lrhip_read_scene_table): the bytes of one of the device tables that move with the geometry
-        (_ffi.TABLE_NODES, TABLE_BVH_TRIANGLES -- with the sentinel behind the last triangle --, TABLE_INSTANCES, TABLE_SHADE_TRIANGLES)
+        (_ffi.TABLE_NODES, TABLE_BVH_TRIANGLES -- with the sentinel behind the last triangle --, TABLE_INSTANCES, TABLE_SHADE_TRIANGLES) or
+        of the object-space vertex table (TABLE_VERTICES)
         as a uint8 array [records, bytes per record]"""
         size = int(self._lib.lrhip_scene_table_bytes(self._ctx, which))
         out = np.empty(size, np.uint8)

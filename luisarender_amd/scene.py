@@ -22,6 +22,19 @@ def aov_channels(component: str) -> int:
     return 1 if component in ("depth", "mask") else 3
 
 
+class _MeshVertexCounts:
+    """the vertex count of every mesh of a view as a read-only sequence (render.check_mesh_vertices looks at one entry)"""
+
+    def __init__(self, view):
+        self._view = view
+
+    def __len__(self) -> int:
+        return int(self._view.mesh_count)
+
+    def __getitem__(self, mesh: int) -> int:
+        return int(self._view.meshes[mesh].vertex_count)
+
+
 class Scene:
     """A parsed + flattened scene (lrhost_scene) and its POD view (lr_scene)."""
 
@@ -93,6 +106,44 @@ class Scene:
         if rc != 0:
             raise HostError(self._lib.lrhost_last_error().decode())
         self._views.clear()
+
+    def set_mesh_vertices(self, mesh: int, positions, normals=None, first: int = 0, recompute_normals: bool = False) -> None:
+        """lrhost_scene_set_mesh_vertices: the host mirror of MegaPathRenderer.set_mesh_vertices -- vertices first .. first + N - 1 of mesh
+        `mesh` get the object-space positions [N, 3] and, if given, the normals [N, 3] (None: kept, or with recompute_normals recomputed
+        for the whole mesh); every instance of the mesh is re-baked and the BVH is refitted when it is built; the tables behind view()
+        change in place (upload again, with keep_film to carry the film on).  float32 numpy arrays only (render.check_mesh_vertices has
+        the rules); HostError for a mesh with an emissive instance."""
+        from .render import check_mesh_vertices
+        if recompute_normals and normals is not None:
+            raise ValueError("set_mesh_vertices: normals must be None with recompute_normals")
+        if check_mesh_vertices(positions, normals, mesh, first, _MeshVertexCounts(self.view())) != "numpy":
+            raise ValueError("set_mesh_vertices: the host scene takes numpy arrays")
+        rc = self._lib.lrhost_scene_set_mesh_vertices(self._handle, int(mesh), int(first), int(positions.shape[0]), positions.ctypes.data,
+                                                      normals.ctypes.data if normals is not None else None,
+                                                      _ffi.MESH_RECOMPUTE_NORMALS if recompute_normals else 0)
+        if rc != 0:
+            raise HostError(self._lib.lrhost_last_error().decode())
+        self._views.clear()
+
+    def instance_mesh(self, instance: int) -> int:
+        """the mesh of an instance: lr_instance.handle.x >> 10, an index into lr_scene.meshes (instances may share a mesh)"""
+        view = self.view()
+        if not 0 <= int(instance) < int(view.instance_count):
+            raise ValueError(f"instance_mesh: instance {instance} out of range ({int(view.instance_count)} instances)")
+        return int(view.instances[int(instance)].handle.x) >> 10
+
+    def mesh_vertices(self, mesh: int) -> tuple[np.ndarray, np.ndarray]:
+        """copies of a mesh's object-space vertex positions and normals -> (positions [V, 3], normals [V, 3]), float32"""
+        view = self.view()
+        if not 0 <= int(mesh) < int(view.mesh_count):
+            raise ValueError(f"mesh_vertices: mesh {mesh} out of range ({int(view.mesh_count)} meshes)")
+        record = view.meshes[int(mesh)]
+        offset, count = int(record.vertex_offset), int(record.vertex_count)
+        if count == 0:
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
+        address = C.addressof(view.vertices.contents) + offset * 32
+        table = np.frombuffer(C.string_at(address, count * 32), np.float32).reshape(count, 8)
+        return np.ascontiguousarray(table[:, 0:3]), np.ascontiguousarray(table[:, 3:6])
 
     def shutter_samples(self, camera: int = 0) -> list[tuple[float, float, int]]:
         """Camera::shutter_samples (src/base/camera.cpp:163-203) -> [(time, weight, spp)]"""
