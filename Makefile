@@ -111,6 +111,9 @@ lrhip_instance_update_FLAGS = -ffp-contract=off -fhip-fp32-correctly-rounded-div
 # lrhip_mesh_update.o holds the kernels that deform a mesh in front of those (csrc/hip/mesh_update_kernels.h); its normal recompute -- sums of cross
 # products, one square root, three divisions -- is held to the host's bits in the same way (tests/test_gpu_mesh_vertices.py)
 lrhip_mesh_update_FLAGS = $(lrhip_instance_update_FLAGS)
+# lrhip_surface.o holds the kernels of the surface queries (csrc/hip/surface_kernel.h); the full one makes real calls -- the texture lookup, the
+# out-of-line albedo / roughness of Disney, Mix and Layered surfaces -- so it takes the variants' safe flag
+lrhip_surface_FLAGS = $(CALL_SAFE_FLAGS)
 $(HIP_OBJ): $(OBJDIR)/%.o: $(HIPDIR)/%.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $($*_FLAGS) -c -o $@ $<

@@ -18,6 +18,8 @@
  *   lrhip_film_reduce              (no reference equivalent: the one collective of the multi-GPU path)
  *   lrhip_trace_rays               (no reference entry point: Geometry::trace_closest / trace_any for the caller's rays)
  *   lrhip_trace_radiance           (no reference entry point: MegakernelPathTracingInstance::Li for the caller's rays)
+ *   lrhip_query_surface            (no reference entry point: Geometry::shading_point, the closure's albedo / roughness and the light's emission
+ *                                  at the caller's hits)
  *   lrhip_set_instance_transforms  (Geometry::update for matrices the caller holds, computed on the device)
  *   lrhip_set_mesh_vertices        (no reference equivalent: new vertex positions for one mesh, re-baked and refitted on the device)
  *   lrhip_get_counters             (no reference equivalent; roofline accounting)
@@ -250,6 +252,72 @@ typedef struct lrhip_radiance_query_params {
 int lrhip_trace_radiance(lrhip_ctx *ctx, const lrhip_radiance_query_params *params);
 /* HIP-event time of the kernel(s) of the last lrhip_trace_radiance call (a host-pointer call: summed over its chunks), in ms; synchronises */
 double lrhip_last_radiance_ms(lrhip_ctx *ctx);
+
+/* Surface queries: what is AT a hit -- world position, normals, uv, material and emission -- for hit records the caller
+ * supplies: what lrhip_trace_rays wrote, or records made from a texel's (inst, prim, u, v).  Picking, the start points and guides of a
+ * lightmap bake, normal and albedo baking.  The reference computes these inside its kernels only (Geometry::shading_point,
+ * src/base/geometry.cpp:345-389; Surface::Closure::albedo / roughness; Light::Closure::evaluate); the AOV integrator sums them per pixel of
+ * the scene's camera.  Camera, integrator and sampler play no part here.
+ *   Which triangle    hit.tri < the BVH's triangle count: the renderer's path.  inst and prim are read from the triangle's record, the caller's
+ *                     copies are ignored, and the point is the one a render shades at this hit, from the baked shading record, bit for bit.
+ *                     hit.tri == LR_INVALID_ID with inst < instance_count and prim inside that instance's mesh: the same quantities from the
+ *                     instance, its triangle and three vertices, with weights (1 - u - v, u, v) -- for callers who hold a texel's
+ *                     (inst, prim, u, v) and no ray.  The two paths differ in the last bits only (world-space against object-space arithmetic).
+ *                     Any other record -- a miss, an id out of range, a non-finite u or v -- gives the INVALID RECORD: 128 zero bytes except
+ *                     inst = prim = surface = light = closure_kind = LR_INVALID_ID.  Every index is checked before it is used: a malformed
+ *                     record never faults.  u and v are not confined to the triangle: a point outside it is extrapolated.
+ *   Viewing direction with rays: wo = -d / |d| (the normalisation rule of lrhip_trace_radiance: a direction whose squared length is within 4e-7
+ *                     of 1 is taken bit for bit), and the emission is the light's towards o.  A ray lrhip_trace_rays would screen makes
+ *                     its record invalid.  With rays == NULL: wo = ng, the surface seen from its front, from p + ng.
+ *                     LRHIP_SURFACE_BACK_FACING = dot(wo, ng) < 0.
+ *   Geometry          p, area (world space), ng (unit, the orientation of cross(e1, e2), never flipped), ns (the interaction's shading normal,
+ *                     face-forwarded to ng: what the AOV `normal` buffer sums), tangent (the shading frame's s: dpdu, or the fallback frame's
+ *                     where the uv determinant is 0), uv.
+ *   Material          where the instance has a surface, the closure is resolved exactly as the shading block resolves it (textures and normal
+ *                     map at uv): n_closure is the normal of its frame, closure_kind its LR_SURFACE_* kind, albedo and roughness
+ *                     Surface::Closure::albedo / roughness as the AOV integrator reports them.  Without a surface: albedo = roughness = 0,
+ *                     n_closure = ns, closure_kind = LR_INVALID_ID.  emission: the light's L towards the ray's origin where the scene has
+ *                     lights and the instance carries LR_SHAPE_HAS_LIGHT (0 from behind a one-sided light), else 0.  surface: the closure
+ *                     index ((tags >> 12) & 4095) or LR_INVALID_ID; light: the light index (tags & 4095) or LR_INVALID_ID.
+ *   LRHIP_SURFACE_GEOMETRY_ONLY  skips material and emission: those fields are written as for "no surface, no light"; surface, light and
+ *                     the flag bits are still reported.  A kernel of its own that holds no texture or closure code.
+ *   Scope             the full query is refused with LRHIP_ERROR_UNSUPPORTED for scenes with Mix / Layered surfaces nested in each other
+ *                     (the AOV integrator refuses them for the same reason); it serves MegaPath, AOV, Direct, Normal and MegaVPTNaive scenes
+ *                     alike.  The geometry-only query serves every uploaded scene.
+ *   Pointers          as for lrhip_trace_rays.  With LRHIP_RAY_DEVICE_POINTERS hits, rays and out are device memory, 16-byte aligned (else
+ *                     LRHIP_ERROR_INVALID), and the call is asynchronous on the context's stream: a trace followed by a surface query needs no
+ *                     host round trip.  Without it they are host memory, staged 2^20 records at a time through context-owned buffers released
+ *                     with the context, and the call synchronises.
+ *   Errors            LRHIP_ERROR_INVALID before any upload, for NULL hits or out with count > 0, unknown flags, misaligned device pointers
+ *                     and count > LRHIP_RAY_MAX_COUNT.
+ *   Determinism       a record's result is a function of (record, ray, scene) only: bit-identical from run to run and wherever the record
+ *                     stands in the batch.  The tables are read as lrhip_update_scene, lrhip_set_instance_transforms and
+ *                     lrhip_set_mesh_vertices left them.  lrhip_last_variant, film, AOV buffers and counters are untouched.                 */
+typedef struct lrhip_surface_point {          /* 128 bytes, eight dwordx4 stores */
+    float p[3];         float area;           /* world position; world-space area of the triangle */
+    float ng[3];        uint32_t flags;       /* unit geometric normal, orientation of cross(e1, e2), never flipped; LRHIP_SURFACE_* bits */
+    float ns[3];        uint32_t inst;        /* the interaction's shading normal (face-forwarded to ng): what the AOV `normal` buffer sums */
+    float tangent[3];   uint32_t prim;        /* shading frame's s (dpdu, or the fallback frame's where the uv determinant is 0) */
+    float n_closure[3]; uint32_t closure_kind;/* normal of the closure's frame (normal map applied); = ns and LR_INVALID_ID without a surface */
+    float uv[2];        float roughness[2];
+    float albedo[3];    uint32_t surface;     /* closure index ((tags >> 12) & 4095) or LR_INVALID_ID */
+    float emission[3];  uint32_t light;       /* the light's L towards the ray's origin; light index (tags & 4095) or LR_INVALID_ID */
+} lrhip_surface_point;
+#define LRHIP_SURFACE_VALID 1u
+#define LRHIP_SURFACE_BACK_FACING 2u
+#define LRHIP_SURFACE_HAS_SURFACE 4u
+#define LRHIP_SURFACE_HAS_LIGHT 8u
+typedef struct lrhip_surface_query_params {
+    const void *hits;   /* lrhip_ray_hit[count]: what lrhip_trace_rays wrote, or records the caller made */
+    const void *rays;   /* lrhip_ray[count] or NULL */
+    void *out;          /* lrhip_surface_point[count] */
+    uint64_t count;     /* 0 is legal and launches nothing; at most LRHIP_RAY_MAX_COUNT */
+    uint32_t flags;     /* LRHIP_RAY_DEVICE_POINTERS, LRHIP_SURFACE_GEOMETRY_ONLY */
+} lrhip_surface_query_params;
+#define LRHIP_SURFACE_GEOMETRY_ONLY 32u
+int lrhip_query_surface(lrhip_ctx *ctx, const lrhip_surface_query_params *params);
+/* HIP-event time of the kernel(s) of the last lrhip_query_surface call (a host-pointer call: summed over its chunks), in ms; synchronises */
+double lrhip_last_surface_ms(lrhip_ctx *ctx);
 
 /* Moving instances on the device: Geometry::update (src/base/geometry.cpp:194-216) for object-to-world matrices the caller holds --
  * an animation frame, a physics step whose matrices are a tensor on the GPU, a drag in an editor -- between two renders or queries, without a

@@ -157,6 +157,18 @@ class RadianceQueryParams(C.Structure):
                 ("flags", u32), ("clamp", f32)]
 
 
+class SurfacePoint(C.Structure):
+    """lrhip_surface_point (include/lrhip.h): one row of the [N, 32] 32-bit buffer behind SurfacePoints"""
+    _fields_ = [("p", f32 * 3), ("area", f32), ("ng", f32 * 3), ("flags", u32), ("ns", f32 * 3), ("inst", u32),
+                ("tangent", f32 * 3), ("prim", u32), ("n_closure", f32 * 3), ("closure_kind", u32), ("uv", f32 * 2), ("roughness", f32 * 2),
+                ("albedo", f32 * 3), ("surface", u32), ("emission", f32 * 3), ("light", u32)]
+
+
+class SurfaceQueryParams(C.Structure):
+    """lrhip_surface_query_params (include/lrhip.h)"""
+    _fields_ = [("hits", C.c_void_p), ("rays", C.c_void_p), ("out", C.c_void_p), ("count", u64), ("flags", u32)]
+
+
 class InstanceUpdateParams(C.Structure):
     """lrhip_instance_update_params (include/lrhip.h)"""
     _fields_ = [("object_to_world", C.c_void_p), ("instances", C.c_void_p), ("count", u64), ("flags", u32)]
@@ -176,8 +188,12 @@ RAY_DEVICE_POINTERS, RAY_ALPHA_TEST = 1, 2  # LRHIP_RAY_DEVICE_POINTERS / LRHIP_
 RADIANCE_ACCUMULATE, RADIANCE_COUNTERS = 4, 8  # LRHIP_RADIANCE_ACCUMULATE / LRHIP_RADIANCE_COUNTERS
 FEAT_QUERY = 65536  # LRHIP_FEAT_QUERY
 MESH_RECOMPUTE_NORMALS = 16  # LRHIP_MESH_RECOMPUTE_NORMALS
+SURFACE_GEOMETRY_ONLY = 32  # LRHIP_SURFACE_GEOMETRY_ONLY
+# lrhip_surface_point::flags: LRHIP_SURFACE_VALID / BACK_FACING / HAS_SURFACE / HAS_LIGHT
+SURFACE_VALID, SURFACE_BACK_FACING, SURFACE_HAS_SURFACE, SURFACE_HAS_LIGHT = 1, 2, 4, 8
 
-STRUCTS = {"lrhip_denoise_params": DenoiseParams, "lrhip_ray": Ray, "lrhip_ray_hit": RayHit, "lrhip_ray_query_params": RayQueryParams,
+STRUCTS = {"lrhip_surface_point": SurfacePoint, "lrhip_surface_query_params": SurfaceQueryParams,
+"lrhip_denoise_params": DenoiseParams, "lrhip_ray": Ray, "lrhip_ray_hit": RayHit, "lrhip_ray_query_params": RayQueryParams,
            "lrhip_radiance_query_params": RadianceQueryParams, "lrhip_instance_update_params": InstanceUpdateParams,
            "lrhip_mesh_update_params": MeshUpdateParams,
            "lr_scene": Scene, "lr_vertex": Vertex, "lr_triangle": Triangle, "lr_alias_entry": AliasEntry,
@@ -297,6 +313,9 @@ def hip_lib(path: str | None = None) -> C.CDLL:
         lib.lrhip_trace_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceQueryParams)]
         lib.lrhip_last_radiance_ms.restype = C.c_double
         lib.lrhip_last_radiance_ms.argtypes = [C.c_void_p]
+        lib.lrhip_query_surface.argtypes = [C.c_void_p, C.POINTER(SurfaceQueryParams)]
+        lib.lrhip_last_surface_ms.restype = C.c_double
+        lib.lrhip_last_surface_ms.argtypes = [C.c_void_p]
         lib.lrhip_set_instance_transforms.argtypes = [C.c_void_p, C.POINTER(InstanceUpdateParams)]
         lib.lrhip_last_instance_update_ms.restype = C.c_double
         lib.lrhip_last_instance_update_ms.argtypes = [C.c_void_p]

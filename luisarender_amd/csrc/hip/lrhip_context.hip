@@ -30,6 +30,7 @@ void release_scene(lrhip_ctx *ctx) {
     ctx->nodes32 = nullptr, ctx->level_nodes = nullptr, ctx->level_offsets.clear();
     for (auto &b : ctx->mesh_adjacency) { b.release(); }
     ctx->mesh_adjacency.clear(), ctx->meshes.clear(), ctx->mesh_light.clear();
+    ctx->surface_meshes_ready = false;
     // the queues of wavefront mode and the pool kernels' state records are sized for the scene (and the memory free at the time): a new
     // scene starts without them (76-89 GB kept until lrhip_destroy starved later allocations on the same GPU)
     ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->pool.release();
@@ -131,6 +132,9 @@ void lrhip_destroy(lrhip_ctx *ctx) {
     if (ctx->update_end) { (void)hipEventDestroy(ctx->update_end); }
     if (ctx->mesh_begin) { (void)hipEventDestroy(ctx->mesh_begin); }
     if (ctx->mesh_end) { (void)hipEventDestroy(ctx->mesh_end); }
+    ctx->surface_meshes.release(), ctx->surface_hits.release(), ctx->surface_out.release();
+    if (ctx->surface_begin) { (void)hipEventDestroy(ctx->surface_begin); }
+    if (ctx->surface_end) { (void)hipEventDestroy(ctx->surface_end); }
     ctx->spill.release(), ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->wf_counts.release(), ctx->wf_accum.release();
     ctx->pool.release(), ctx->counters.release(), ctx->work_counter.release(), ctx->scene_record.release();
     if (ctx->ev_begin) { (void)hipEventDestroy(ctx->ev_begin); }

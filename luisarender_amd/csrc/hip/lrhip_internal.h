@@ -10,6 +10,7 @@
 //   lrhip_denoise.hip    the edge-avoiding wavelet filter over the AOV buffers (denoise_kernels.h)
 //   lrhip_raycast.hip    ray queries: closest hit / occlusion for caller-supplied rays (raycast_kernel.h)
 //   lrhip_radiance.hip   radiance queries: MegaPath's estimator along caller-supplied rays (the kFeatQuery kernels of megapath_kernel.h)
+//   lrhip_surface.hip    surface queries: position, normals, uv, material and emission at caller-supplied hits (surface_kernel.h)
 //   lrhip_instance_update.hip  moving instances on the device: re-bake, refit and re-quantise (instance_update_kernels.h); the table test hook
 //   lrhip_mesh_update.hip      deforming a mesh on the device: vertex write, normal recompute, marking (mesh_update_kernels.h), then the re-bake and refit
 // Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
@@ -200,6 +201,16 @@ struct lrhip_ctx {
     hipEvent_t mesh_begin{nullptr}, mesh_end{nullptr};
     double mesh_ms{0.};
     bool mesh_pending{false};
+    // surface queries (lrhip_surface.hip).  Of the uploaded scene: the lr_mesh table in device memory (what bounds `prim` of a record that
+    // names an instance), copied on the first query after an upload (surface_meshes_ready; release_scene clears it).  Of the context: the
+    // staging buffers of a host-pointer call (hit records, results; the rays go through raycast_rays) -- they grow on demand and outlive the
+    // scene --, the events around the last launch, the kernel time of the last call's finished launches and whether one is still to be read
+    // (lrhip_last_surface_ms)
+    lrh::DeviceBuffer surface_meshes, surface_hits, surface_out;
+    bool surface_meshes_ready{false};
+    hipEvent_t surface_begin{nullptr}, surface_end{nullptr};
+    double surface_ms{0.};
+    bool surface_pending{false};
 };
 
 namespace lrh {

@@ -101,6 +101,33 @@ def check_radiance_args(rays, spp: int = 1, spp_begin: int = 0, streams=None, cl
     return kind
 
 
+def check_surface_args(hits=None, rays=None, device: int | None = None) -> str:
+    """What MegaPathRenderer.surface accepts (no device needed).  hits: a RayHits, or a float32 [N, 8] array of lrhip_ray_hit records
+    (t, u, v, inst, prim, tri, 0, 0 -- the ids as the bits of uint32), or None: then rays are traced first.  rays: what check_rays accepts,
+    or None: every point is seen from its front.  Both are of one kind (numpy, or torch on one GPU), contiguous, and have the same N.
+    Returns check_rays' answer; ValueError for anything else."""
+    if hits is None and rays is None:
+        raise ValueError("surface: neither hits nor rays")
+    kind = None
+    if rays is not None:
+        kind = check_rays(rays, device)
+    if hits is not None:
+        buffer = hits.buffer if isinstance(hits, RayHits) else hits
+        try:
+            hits_kind = check_rays(buffer, device)
+        except ValueError as e:
+            raise ValueError(str(e).replace("trace: rays", "surface: hits").replace("trace: the ray tensor", "surface: the hit tensor")
+                             .replace("(ox, oy, oz, t_min, dx, dy, dz, t_max)", "(t, u, v, inst, prim, tri, 0, 0)")) from None
+        if kind is not None and hits_kind != kind:
+            raise ValueError(f"surface: hits are a {hits_kind} array, rays a {kind} array")
+        if kind is not None and int(buffer.shape[0]) != int(rays.shape[0]):
+            raise ValueError(f"surface: {int(buffer.shape[0])} hits for {int(rays.shape[0])} rays")
+        if kind == "torch" and buffer.device != rays.device:
+            raise ValueError(f"surface: hits are on {buffer.device}, rays on {rays.device}")
+        kind = hits_kind
+    return kind
+
+
 def check_instance_transforms(matrices, instances=None, instance_count: int | None = None, device: int | None = None) -> str:
     """What MegaPathRenderer.set_instance_transforms and Scene.set_instance_transforms accept (no device needed).  matrices: float32,
     contiguous, [N, 4, 4] or [N, 16] in COLUMN-MAJOR storage -- matrices[i, c, r] (flat: [i, 4 c + r]) is row r of column c, the layout of
@@ -230,6 +257,48 @@ class RayHits:
     @property
     def hit(self):
         return self.inst != self._invalid
+
+    def __len__(self) -> int:
+        return int(self.buffer.shape[0])
+
+
+class SurfacePoints:
+    """Results of MegaPathRenderer.surface: views (no copies) of ONE [N, 32] 32-bit buffer of lrhip_surface_point records -- `buffer`, a
+    float32 numpy array or, for the torch path, the float32 tensor on the device.  p, ng, ns, tangent, n_closure, albedo, emission: [N, 3];
+    uv, roughness: [N, 2]; area: [N]; inst, prim, surface, light, closure_kind, flags: uint32 (torch: int32, LR_INVALID_ID reads -1);
+    valid, back_facing, has_surface, has_light: the flag bits as bool."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        if isinstance(buffer, np.ndarray):
+            ids = buffer.view(np.uint32)
+        else:
+            import torch
+            ids = buffer.view(torch.int32)
+        self.p, self.area = buffer[:, 0:3], buffer[:, 3]
+        self.ng, self.flags = buffer[:, 4:7], ids[:, 7]
+        self.ns, self.inst = buffer[:, 8:11], ids[:, 11]
+        self.tangent, self.prim = buffer[:, 12:15], ids[:, 15]
+        self.n_closure, self.closure_kind = buffer[:, 16:19], ids[:, 19]
+        self.uv, self.roughness = buffer[:, 20:22], buffer[:, 22:24]
+        self.albedo, self.surface = buffer[:, 24:27], ids[:, 27]
+        self.emission, self.light = buffer[:, 28:31], ids[:, 31]
+
+    @property
+    def valid(self):
+        return (self.flags & _ffi.SURFACE_VALID) != 0
+
+    @property
+    def back_facing(self):
+        return (self.flags & _ffi.SURFACE_BACK_FACING) != 0
+
+    @property
+    def has_surface(self):
+        return (self.flags & _ffi.SURFACE_HAS_SURFACE) != 0
+
+    @property
+    def has_light(self):
+        return (self.flags & _ffi.SURFACE_HAS_LIGHT) != 0
 
     def __len__(self) -> int:
         return int(self.buffer.shape[0])
@@ -432,6 +501,44 @@ class MegaPathRenderer:
     def last_radiance_ms(self) -> float:
         """lrhip_last_radiance_ms: HIP-event time of the kernel(s) of the last radiance()"""
         return float(self._lib.lrhip_last_radiance_ms(self._ctx))
+
+    def surface(self, hits=None, rays=None, geometry_only: bool = False, sync: bool = True) -> SurfacePoints:
+        """lrhip_query_surface (lrhip.h has the semantics): what is at each hit -- position, normals, uv, the closure's albedo and roughness,
+        the light's emission.  hits, rays: what check_surface_args accepts.  hits: a RayHits from trace(), or [N, 8] records the caller made
+        (tri = 0xffffffff with inst, prim, u, v names a point without a ray); None: rays are traced first, on the same stream.  rays: the
+        viewing rays (emission and back_facing are taken from them), or None: every point is seen from its front.  geometry_only: material and
+        emission are skipped (zeros) -- this form serves every scene.  numpy arrays go through host pointers; torch tensors on this renderer's
+        GPU are read in place and the result stays on the device (synchronisation as in trace())."""
+        kind = check_surface_args(hits, rays, self._device)
+        if kind == "torch" and sync:
+            import torch
+            torch.cuda.current_stream((rays if rays is not None else getattr(hits, "buffer", hits)).device).synchronize()
+        if hits is None:  # (the trace and the query are ordered on the context's stream: no host round trip between them)
+            hits = self.trace(rays, sync=False) if kind == "torch" else self.trace(rays)
+        buffer = hits.buffer if isinstance(hits, RayHits) else hits
+        n = int(buffer.shape[0])
+        p = _ffi.SurfaceQueryParams()
+        p.count = n
+        p.flags = _ffi.SURFACE_GEOMETRY_ONLY if geometry_only else 0
+        if kind == "numpy":
+            out = np.empty((n, 32), np.float32)
+            p.hits, p.out = buffer.ctypes.data, out.ctypes.data
+            p.rays = rays.ctypes.data if rays is not None else None
+            self._check(self._lib.lrhip_query_surface(self._ctx, C.byref(p)))
+            return SurfacePoints(out)
+        import torch
+        out = torch.empty((n, 32), dtype=torch.float32, device=buffer.device)
+        p.hits, p.out = buffer.data_ptr(), out.data_ptr()
+        p.rays = rays.data_ptr() if rays is not None else None
+        p.flags |= _ffi.RAY_DEVICE_POINTERS
+        self._check(self._lib.lrhip_query_surface(self._ctx, C.byref(p)))
+        if sync:
+            self.synchronize()
+        return SurfacePoints(out)
+
+    def last_surface_ms(self) -> float:
+        """lrhip_last_surface_ms: HIP-event time of the kernel(s) of the last surface()"""
+        return float(self._lib.lrhip_last_surface_ms(self._ctx))
 
     def set_instance_transforms(self, matrices, instances=None, sync: bool = True) -> None:
         """lrhip_set_instance_transforms (lrhip.h has the semantics): move instances of the uploaded scene on the device -- their records, baked
