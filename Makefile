@@ -114,6 +114,13 @@ lrhip_mesh_update_FLAGS = $(lrhip_instance_update_FLAGS)
 # lrhip_surface.o holds the kernels of the surface queries (csrc/hip/surface_kernel.h); the full one makes real calls -- the texture lookup, the
 # out-of-line albedo / roughness of Disney, Mix and Layered surfaces -- so it takes the variants' safe flag
 lrhip_surface_FLAGS = $(CALL_SAFE_FLAGS)
+# lrhip_bsdf.o holds the kernels of the BSDF queries (csrc/hip/bsdf_kernel.h): the texture lookup and the out-of-line evaluate / sample of Disney,
+# Mix and Layered surfaces are real calls, so it takes the variants' safe flag.  It is also built with the arithmetic of the reference-pinned
+# oracle, like the volumetric kernel: a query hands ONE closure answer to the caller, where a render sums millions, and HIPFLAGS' arithmetic
+# shows in single answers -- r / r of Glass' reflection probability under total internal reflection comes out of the approximate division as
+# 1 - 2^-24, which leaves a pdf of 1e-8 where the reference has 0, and the cancellations of the visible-normal slope sampling (ggx_sample11)
+# turn last-bit differences of v_rcp / v_sqrt and of contraction into sampled directions 2e-3 away from the oracle's (measured)
+lrhip_bsdf_FLAGS = $(CALL_SAFE_FLAGS) -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-approx-func
 $(HIP_OBJ): $(OBJDIR)/%.o: $(HIPDIR)/%.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $($*_FLAGS) -c -o $@ $<

@@ -20,6 +20,7 @@
  *   lrhip_trace_radiance           (no reference entry point: MegakernelPathTracingInstance::Li for the caller's rays)
  *   lrhip_query_surface            (no reference entry point: Geometry::shading_point, the closure's albedo / roughness and the light's emission
  *                                  at the caller's hits)
+ *   lrhip_query_bsdf               (no reference entry point: Surface::Closure::evaluate / sample at the caller's hits)
  *   lrhip_set_instance_transforms  (Geometry::update for matrices the caller holds, computed on the device)
  *   lrhip_set_mesh_vertices        (no reference equivalent: new vertex positions for one mesh, re-baked and refitted on the device)
  *   lrhip_get_counters             (no reference equivalent; roofline accounting)
@@ -318,6 +319,61 @@ typedef struct lrhip_surface_query_params {
 int lrhip_query_surface(lrhip_ctx *ctx, const lrhip_surface_query_params *params);
 /* HIP-event time of the kernel(s) of the last lrhip_query_surface call (a host-pointer call: summed over its chunks), in ms; synchronises */
 double lrhip_last_surface_ms(lrhip_ctx *ctx);
+
+/* BSDF queries: the closure's answer at a hit the caller names -- Surface::Closure::evaluate for a direction the caller gives,
+ * or Surface::Closure::sample for three random numbers the caller gives (src/base/surface.cpp:35-68) -- the missing piece between
+ * lrhip_query_surface (what is at a hit) and lrhip_trace_radiance (the whole estimator): a direct-lighting estimator of the caller's own, path
+ * guiding, an integrator written as tensor operations over batches of rays, a material preview.  Camera, integrator and sampler play no part:
+ * the query is a pure function of its inputs.
+ *   Which triangle    exactly as for lrhip_query_surface: hit.tri < the BVH's triangle count is the baked path, hit.tri == LR_INVALID_ID with
+ *                     valid (inst, prim) the instance path; every index is checked before it is used, a non-finite u or v gives the invalid record.
+ *   Viewing direction exactly as for lrhip_query_surface: wo = -d / |d| of the record's ray (a direction whose squared length is within 4e-7 of 1
+ *                     is taken bit for bit); a ray lrhip_trace_rays would screen makes its record invalid; rays == NULL: wo = ng.
+ *   dirs              one float4 per record.  LRHIP_BSDF_EVALUATE: (wi.x, wi.y, wi.z, ignored) -- wi in world space, pointing AWAY from the
+ *                     surface, of any length: it is normalised by wo's rule; a zero or non-finite wi gives the invalid record.
+ *                     LRHIP_BSDF_SAMPLE: (u_lobe, u_x, u_y, ignored) -- the three numbers Surface::Closure::sample draws, in the order the
+ *                     path tracer draws them; a non-finite one gives the invalid record.  No sampler is touched.
+ *   What is computed  the closure is resolved as the shading block resolves it (textures and normal map at uv), then evaluated or sampled by
+ *                     the calls the MegaPath shading block makes, for radiance transport, from outside (eta_i = 1).  f INCLUDES |cos theta_i|
+ *                     (Surface::Evaluation::f as the path tracer consumes it: throughput *= f / pdf).  Layered surfaces estimate f by a random
+ *                     walk seeded from the bits of p and the directions: deterministic, but a different draw at another point.
+ *   Result            evaluate: (f, pdf, the unit wi that was used, event = 0).  sample: (f, pdf, the sampled world-space wi, event =
+ *                     LRHIP_BSDF_EVENT_*).  pdf = 0 is a failed sample: its f and wi are what the closure left there and may be non-finite (a
+ *                     total internal reflection), as in the reference, whose path tracer tests pdf > 0 first.  THE INVALID RECORD -- an invalid hit record, ray or dirs, or a
+ *                     valid hit on an instance without a surface -- is 32 zero bytes except event = LR_INVALID_ID.  A malformed record never faults.
+ *   Scope             scenes of every integrator with basic closures, Disney, Mix (trees of basic and Disney leaves included) and Layered;
+ *                     LRHIP_ERROR_UNSUPPORTED for scenes with Mix / Layered surfaces nested in each other, as the full surface query.
+ *   Pointers          as for lrhip_query_surface.  With LRHIP_RAY_DEVICE_POINTERS hits, rays, dirs and out are device memory, 16-byte aligned
+ *                     (else LRHIP_ERROR_INVALID), and the call is asynchronous on the context's stream: trace, then sample, needs no host round
+ *                     trip.  Without it they are host memory, staged 2^20 records at a time through context-owned buffers released with the
+ *                     context, and the call synchronises.
+ *   Errors            LRHIP_ERROR_INVALID before any upload, for NULL hits, dirs or out with count > 0, unknown flags, an unknown mode,
+ *                     misaligned device pointers and count > LRHIP_RAY_MAX_COUNT.
+ *   Determinism       a record's result is a function of (record, ray, dirs, scene) only: bit-identical from run to run and wherever the record
+ *                     stands in the batch.  lrhip_last_variant, film, AOV buffers and counters are untouched.
+ *   Not done          nested Mix / Layered, importance transport, the closure's eta (Russian roulette), opacity, light sampling queries.     */
+typedef struct lrhip_bsdf_result {            /* 32 bytes, two dwordx4 stores */
+    float f[3];         float pdf;            /* value * |cos theta_i|; solid-angle density of wi */
+    float wi[3];        uint32_t event;       /* unit world-space direction; LRHIP_BSDF_EVENT_* (evaluate: 0), LR_INVALID_ID in the invalid record */
+} lrhip_bsdf_result;
+#define LRHIP_BSDF_EVALUATE 0u
+#define LRHIP_BSDF_SAMPLE 1u
+#define LRHIP_BSDF_EVENT_REFLECT 0u           /* Surface::event_reflect / _enter / _exit / _through (src/base/surface.h:46-50) */
+#define LRHIP_BSDF_EVENT_ENTER 1u
+#define LRHIP_BSDF_EVENT_EXIT 2u
+#define LRHIP_BSDF_EVENT_THROUGH 4u
+typedef struct lrhip_bsdf_query_params {
+    const void *hits;   /* lrhip_ray_hit[count]: what lrhip_trace_rays wrote, or records the caller made */
+    const void *rays;   /* lrhip_ray[count] or NULL */
+    const void *dirs;   /* float[4][count]: (wi, -) or (u_lobe, u_x, u_y, -) */
+    void *out;          /* lrhip_bsdf_result[count] */
+    uint64_t count;     /* 0 is legal and launches nothing; at most LRHIP_RAY_MAX_COUNT */
+    uint32_t mode;      /* LRHIP_BSDF_EVALUATE or LRHIP_BSDF_SAMPLE */
+    uint32_t flags;     /* LRHIP_RAY_DEVICE_POINTERS */
+} lrhip_bsdf_query_params;
+int lrhip_query_bsdf(lrhip_ctx *ctx, const lrhip_bsdf_query_params *params);
+/* HIP-event time of the kernel(s) of the last lrhip_query_bsdf call (a host-pointer call: summed over its chunks), in ms; synchronises */
+double lrhip_last_bsdf_ms(lrhip_ctx *ctx);
 
 /* Moving instances on the device: Geometry::update (src/base/geometry.cpp:194-216) for object-to-world matrices the caller holds --
  * an animation frame, a physics step whose matrices are a tensor on the GPU, a drag in an editor -- between two renders or queries, without a

@@ -169,6 +169,17 @@ class SurfaceQueryParams(C.Structure):
     _fields_ = [("hits", C.c_void_p), ("rays", C.c_void_p), ("out", C.c_void_p), ("count", u64), ("flags", u32)]
 
 
+class BsdfResult(C.Structure):
+    """lrhip_bsdf_result (include/lrhip.h): one row of the [N, 8] 32-bit buffer behind BsdfResults"""
+    _fields_ = [("f", f32 * 3), ("pdf", f32), ("wi", f32 * 3), ("event", u32)]
+
+
+class BsdfQueryParams(C.Structure):
+    """lrhip_bsdf_query_params (include/lrhip.h)"""
+    _fields_ = [("hits", C.c_void_p), ("rays", C.c_void_p), ("dirs", C.c_void_p), ("out", C.c_void_p), ("count", u64), ("mode", u32),
+                ("flags", u32)]
+
+
 class InstanceUpdateParams(C.Structure):
     """lrhip_instance_update_params (include/lrhip.h)"""
     _fields_ = [("object_to_world", C.c_void_p), ("instances", C.c_void_p), ("count", u64), ("flags", u32)]
@@ -191,8 +202,12 @@ MESH_RECOMPUTE_NORMALS = 16  # LRHIP_MESH_RECOMPUTE_NORMALS
 SURFACE_GEOMETRY_ONLY = 32  # LRHIP_SURFACE_GEOMETRY_ONLY
 # lrhip_surface_point::flags: LRHIP_SURFACE_VALID / BACK_FACING / HAS_SURFACE / HAS_LIGHT
 SURFACE_VALID, SURFACE_BACK_FACING, SURFACE_HAS_SURFACE, SURFACE_HAS_LIGHT = 1, 2, 4, 8
+BSDF_EVALUATE, BSDF_SAMPLE = 0, 1  # lrhip_bsdf_query_params::mode: LRHIP_BSDF_EVALUATE / LRHIP_BSDF_SAMPLE
+# lrhip_bsdf_result::event: LRHIP_BSDF_EVENT_REFLECT / ENTER / EXIT / THROUGH (LR_INVALID_ID in the invalid record)
+BSDF_EVENT_REFLECT, BSDF_EVENT_ENTER, BSDF_EVENT_EXIT, BSDF_EVENT_THROUGH = 0, 1, 2, 4
 
 STRUCTS = {"lrhip_surface_point": SurfacePoint, "lrhip_surface_query_params": SurfaceQueryParams,
+"lrhip_bsdf_result": BsdfResult, "lrhip_bsdf_query_params": BsdfQueryParams,
 "lrhip_denoise_params": DenoiseParams, "lrhip_ray": Ray, "lrhip_ray_hit": RayHit, "lrhip_ray_query_params": RayQueryParams,
            "lrhip_radiance_query_params": RadianceQueryParams, "lrhip_instance_update_params": InstanceUpdateParams,
            "lrhip_mesh_update_params": MeshUpdateParams,
@@ -316,6 +331,9 @@ def hip_lib(path: str | None = None) -> C.CDLL:
         lib.lrhip_query_surface.argtypes = [C.c_void_p, C.POINTER(SurfaceQueryParams)]
         lib.lrhip_last_surface_ms.restype = C.c_double
         lib.lrhip_last_surface_ms.argtypes = [C.c_void_p]
+        lib.lrhip_query_bsdf.argtypes = [C.c_void_p, C.POINTER(BsdfQueryParams)]
+        lib.lrhip_last_bsdf_ms.restype = C.c_double
+        lib.lrhip_last_bsdf_ms.argtypes = [C.c_void_p]
         lib.lrhip_set_instance_transforms.argtypes = [C.c_void_p, C.POINTER(InstanceUpdateParams)]
         lib.lrhip_last_instance_update_ms.restype = C.c_double
         lib.lrhip_last_instance_update_ms.argtypes = [C.c_void_p]

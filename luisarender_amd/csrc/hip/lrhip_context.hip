@@ -135,6 +135,9 @@ void lrhip_destroy(lrhip_ctx *ctx) {
     ctx->surface_meshes.release(), ctx->surface_hits.release(), ctx->surface_out.release();
     if (ctx->surface_begin) { (void)hipEventDestroy(ctx->surface_begin); }
     if (ctx->surface_end) { (void)hipEventDestroy(ctx->surface_end); }
+    ctx->bsdf_dirs.release(), ctx->bsdf_out.release();
+    if (ctx->bsdf_begin) { (void)hipEventDestroy(ctx->bsdf_begin); }
+    if (ctx->bsdf_end) { (void)hipEventDestroy(ctx->bsdf_end); }
     ctx->spill.release(), ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->wf_counts.release(), ctx->wf_accum.release();
     ctx->pool.release(), ctx->counters.release(), ctx->work_counter.release(), ctx->scene_record.release();
     if (ctx->ev_begin) { (void)hipEventDestroy(ctx->ev_begin); }

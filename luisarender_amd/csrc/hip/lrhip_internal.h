@@ -11,6 +11,7 @@
 //   lrhip_raycast.hip    ray queries: closest hit / occlusion for caller-supplied rays (raycast_kernel.h)
 //   lrhip_radiance.hip   radiance queries: MegaPath's estimator along caller-supplied rays (the kFeatQuery kernels of megapath_kernel.h)
 //   lrhip_surface.hip    surface queries: position, normals, uv, material and emission at caller-supplied hits (surface_kernel.h)
+//   lrhip_bsdf.hip       BSDF queries: the closure evaluated or sampled at caller-supplied hits (bsdf_kernel.h)
 //   lrhip_instance_update.hip  moving instances on the device: re-bake, refit and re-quantise (instance_update_kernels.h); the table test hook
 //   lrhip_mesh_update.hip      deforming a mesh on the device: vertex write, normal recompute, marking (mesh_update_kernels.h), then the re-bake and refit
 // Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
@@ -211,6 +212,17 @@ struct lrhip_ctx {
     hipEvent_t surface_begin{nullptr}, surface_end{nullptr};
     double surface_ms{0.};
     bool surface_pending{false};
+    // BSDF queries (lrhip_bsdf.hip).  Of the uploaded scene: the kFeatDisney / kFeatMix / kFeatLayered bits of its surfaces THEMSELVES,
+    // whatever the integrator (`features` above is what the renderer's kernel must hold: the sibling integrators set every closure bit in
+    // it and the volumetric one clears them) -- what picks the query's kernel.  Of the context: the staging buffers of a host-pointer call
+    // (dirs, results; the hit records go through surface_hits and the rays through raycast_rays) -- they grow on demand and outlive the
+    // scene --, the events around the last launch, the kernel time of the last call's finished launches and whether one is still to be
+    // read (lrhip_last_bsdf_ms).  The lr_mesh table is the surface queries' (surface_meshes)
+    uint32_t closure_features{0u};
+    lrh::DeviceBuffer bsdf_dirs, bsdf_out;
+    hipEvent_t bsdf_begin{nullptr}, bsdf_end{nullptr};
+    double bsdf_ms{0.};
+    bool bsdf_pending{false};
 };
 
 namespace lrh {

@@ -436,6 +436,8 @@ int upload_scene_tables(lrhip_ctx *ctx, const lr_scene *s) {
         LR_UP(upload(ctx, shade.data(), shade.size(), &d.shade_tris));
     }
     LR_UP(upload_surfaces(ctx, s));
+    // the surfaces' own closure bits, before the integrator's class rewrites ctx->features below: what picks a BSDF query's kernel
+    ctx->closure_features = ctx->features & (lrd::kFeatDisney | lrd::kFeatMix | lrd::kFeatLayered);
     LR_UP(upload_lights(ctx, s));
     set_camera(d, s);
     LR_UP(upload_environment(ctx, s));
@@ -609,6 +611,7 @@ int lrhip_upload_scene(lrhip_ctx *ctx, const lr_scene *s) {
         return fail(LRHIP_ERROR_INVALID, "lrhip_upload_scene: the BVH must have one-triangle leaves (lrhost_scene_build_accel builds them)");
     }
     ctx->features = s->any_non_opaque != 0u ? lrd::kFeatAlpha : 0u;
+    ctx->closure_features = 0u;
     ctx->env_tree = false;
     // a leaf names its triangle in 27 bits (the sentinel of the empty slots is one more); the traversal loop addresses packets and leaf
     // triangles by 32-bit byte offsets from their table bases (64 B x 2^26 packets, 48 B x 89 478 484 triangles = 4 GiB)

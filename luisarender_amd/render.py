@@ -36,10 +36,10 @@ def aov_file_name(camera_file: str, component: str, n: int, dump: str) -> str:
     return os.path.join(parent, f"{stem}_{component}{'' if dump == 'final' else f'_{n:05d}'}{ext}")
 
 
-def check_rays(rays, device: int | None = None) -> str:
+def check_rays(rays, device: int | None = None, prefix: str = "trace") -> str:
     """What MegaPathRenderer.trace accepts (no device needed): a C-contiguous float32 numpy array [N, 8] laid out (ox, oy, oz, t_min,
     dx, dy, dz, t_max) -> "numpy", or a contiguous float32 torch tensor of that shape on GPU `device` (None: any GPU) -> "torch".
-    ValueError for anything else."""
+    ValueError for anything else; `prefix` names the caller in its message."""
     if isinstance(rays, np.ndarray):
         kind = "numpy"
         contiguous = rays.flags["C_CONTIGUOUS"]
@@ -50,17 +50,17 @@ def check_rays(rays, device: int | None = None) -> str:
         contiguous = rays.is_contiguous()
         is_float32 = rays.dtype == torch.float32
         if rays.device.type != "cuda":
-            raise ValueError(f"trace: the ray tensor is on {rays.device}, not on a GPU")
+            raise ValueError(f"{prefix}: the ray tensor is on {rays.device}, not on a GPU")
         if device is not None and rays.device.index != device:
-            raise ValueError(f"trace: the ray tensor is on {rays.device}, the renderer on GPU {device}")
+            raise ValueError(f"{prefix}: the ray tensor is on {rays.device}, the renderer on GPU {device}")
     else:
-        raise ValueError(f"trace: rays must be a numpy array or a torch tensor, not {type(rays).__name__}")
+        raise ValueError(f"{prefix}: rays must be a numpy array or a torch tensor, not {type(rays).__name__}")
     if not is_float32:
-        raise ValueError(f"trace: rays must be float32, not {rays.dtype}")
+        raise ValueError(f"{prefix}: rays must be float32, not {rays.dtype}")
     if rays.ndim != 2 or rays.shape[1] != 8:
-        raise ValueError(f"trace: rays must have shape [N, 8] (ox, oy, oz, t_min, dx, dy, dz, t_max), not {tuple(rays.shape)}")
+        raise ValueError(f"{prefix}: rays must have shape [N, 8] (ox, oy, oz, t_min, dx, dy, dz, t_max), not {tuple(rays.shape)}")
     if not contiguous:
-        raise ValueError("trace: rays must be contiguous")
+        raise ValueError(f"{prefix}: rays must be contiguous")
     return kind
 
 
@@ -101,30 +101,68 @@ def check_radiance_args(rays, spp: int = 1, spp_begin: int = 0, streams=None, cl
     return kind
 
 
-def check_surface_args(hits=None, rays=None, device: int | None = None) -> str:
+def check_surface_args(hits=None, rays=None, device: int | None = None, prefix: str | None = None) -> str:
     """What MegaPathRenderer.surface accepts (no device needed).  hits: a RayHits, or a float32 [N, 8] array of lrhip_ray_hit records
     (t, u, v, inst, prim, tri, 0, 0 -- the ids as the bits of uint32), or None: then rays are traced first.  rays: what check_rays accepts,
     or None: every point is seen from its front.  Both are of one kind (numpy, or torch on one GPU), contiguous, and have the same N.
-    Returns check_rays' answer; ValueError for anything else."""
+    Returns check_rays' answer; ValueError for anything else.  `prefix` names the caller in every message (None: "surface", and "trace" where
+    check_rays speaks about the rays)."""
+    own, of_rays = prefix or "surface", prefix or "trace"
     if hits is None and rays is None:
-        raise ValueError("surface: neither hits nor rays")
+        raise ValueError(f"{own}: neither hits nor rays")
     kind = None
     if rays is not None:
-        kind = check_rays(rays, device)
+        kind = check_rays(rays, device, of_rays)
     if hits is not None:
         buffer = hits.buffer if isinstance(hits, RayHits) else hits
         try:
-            hits_kind = check_rays(buffer, device)
+            hits_kind = check_rays(buffer, device, of_rays)
         except ValueError as e:
-            raise ValueError(str(e).replace("trace: rays", "surface: hits").replace("trace: the ray tensor", "surface: the hit tensor")
+            raise ValueError(str(e).replace(f"{of_rays}: rays", f"{own}: hits").replace(f"{of_rays}: the ray tensor", f"{own}: the hit tensor")
                              .replace("(ox, oy, oz, t_min, dx, dy, dz, t_max)", "(t, u, v, inst, prim, tri, 0, 0)")) from None
         if kind is not None and hits_kind != kind:
-            raise ValueError(f"surface: hits are a {hits_kind} array, rays a {kind} array")
+            raise ValueError(f"{own}: hits are a {hits_kind} array, rays a {kind} array")
         if kind is not None and int(buffer.shape[0]) != int(rays.shape[0]):
-            raise ValueError(f"surface: {int(buffer.shape[0])} hits for {int(rays.shape[0])} rays")
+            raise ValueError(f"{own}: {int(buffer.shape[0])} hits for {int(rays.shape[0])} rays")
         if kind == "torch" and buffer.device != rays.device:
-            raise ValueError(f"surface: hits are on {buffer.device}, rays on {rays.device}")
+            raise ValueError(f"{own}: hits are on {buffer.device}, rays on {rays.device}")
         kind = hits_kind
+    return kind
+
+
+def check_bsdf_args(hits, dirs, rays=None, device: int | None = None, what: str = "wi") -> str:
+    """What MegaPathRenderer.bsdf_evaluate / bsdf_sample accept (no device needed).  hits: a RayHits, or a float32 [N, 8] array of lrhip_ray_hit
+    records, as check_surface_args takes them.  dirs (`what` names it in messages): float32 [N, 3] or [N, 4] -- wi, or (u_lobe, u_x, u_y); an
+    [N, 4] array must be contiguous (it is read in place), an [N, 3] one is padded by a copy.  rays: what check_rays accepts, or None.  All are
+    of one kind (numpy, or torch on one GPU) and have the same N.  Returns check_rays' answer; TypeError for an argument that is no array or
+    tensor at all, ValueError for anything else."""
+    for name, a in (("hits", hits.buffer if isinstance(hits, RayHits) else hits), (what, dirs)):
+        if not isinstance(a, np.ndarray) and not (type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")):
+            raise TypeError(f"bsdf: {name} must be a numpy array or a torch tensor, not {type(a).__name__}")
+    if rays is not None and not isinstance(rays, np.ndarray) and not (type(rays).__module__.split(".")[0] == "torch" and hasattr(rays, "data_ptr")):
+        raise TypeError(f"bsdf: rays must be a numpy array, a torch tensor or None, not {type(rays).__name__}")
+    kind = check_surface_args(hits, rays, device, prefix="bsdf")
+    n = len(hits)
+    if kind == "numpy":
+        if not isinstance(dirs, np.ndarray):
+            raise ValueError(f"bsdf: hits are a numpy array, {what} a torch tensor")
+        is_float32, contiguous = dirs.dtype == np.float32, dirs.flags["C_CONTIGUOUS"]
+    else:
+        import torch
+        if isinstance(dirs, np.ndarray):
+            raise ValueError(f"bsdf: hits are a torch tensor, {what} a numpy array")
+        is_float32, contiguous = dirs.dtype == torch.float32, dirs.is_contiguous()
+        buffer = hits.buffer if isinstance(hits, RayHits) else hits
+        if dirs.device != buffer.device:
+            raise ValueError(f"bsdf: hits are on {buffer.device}, {what} on {dirs.device}")
+    if not is_float32:
+        raise ValueError(f"bsdf: {what} must be float32, not {dirs.dtype}")
+    if dirs.ndim != 2 or dirs.shape[1] not in (3, 4):
+        raise ValueError(f"bsdf: {what} must have shape [N, 3] or [N, 4], not {tuple(dirs.shape)}")
+    if int(dirs.shape[0]) != n:
+        raise ValueError(f"bsdf: {n} hits for {int(dirs.shape[0])} rows of {what}")
+    if dirs.shape[1] == 4 and not contiguous:
+        raise ValueError(f"bsdf: an [N, 4] {what} is read in place and must be contiguous")
     return kind
 
 
@@ -299,6 +337,30 @@ class SurfacePoints:
     @property
     def has_light(self):
         return (self.flags & _ffi.SURFACE_HAS_LIGHT) != 0
+
+    def __len__(self) -> int:
+        return int(self.buffer.shape[0])
+
+
+class BsdfResults:
+    """Results of MegaPathRenderer.bsdf_evaluate / bsdf_sample: views (no copies) of ONE [N, 8] 32-bit buffer of lrhip_bsdf_result records --
+    `buffer`, a float32 numpy array or, for the torch path, the float32 tensor on the device.  f (the closure's value times |cos theta_i|)
+    and wi (unit, world space): [N, 3]; pdf: [N]; event: uint32 (torch: int32, LR_INVALID_ID reads -1), _ffi.BSDF_EVENT_*; valid: bool,
+    false for the invalid record."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        if isinstance(buffer, np.ndarray):
+            ids = buffer.view(np.uint32)
+        else:
+            import torch
+            ids = buffer.view(torch.int32)
+        self.f, self.pdf = buffer[:, 0:3], buffer[:, 3]
+        self.wi, self.event = buffer[:, 4:7], ids[:, 7]
+
+    @property
+    def valid(self):
+        return self.event != (0xFFFFFFFF if isinstance(self.buffer, np.ndarray) else -1)
 
     def __len__(self) -> int:
         return int(self.buffer.shape[0])
@@ -539,6 +601,54 @@ class MegaPathRenderer:
     def last_surface_ms(self) -> float:
         """lrhip_last_surface_ms: HIP-event time of the kernel(s) of the last surface()"""
         return float(self._lib.lrhip_last_surface_ms(self._ctx))
+
+    def _bsdf(self, mode: int, hits, dirs, rays, sync: bool, what: str) -> BsdfResults:
+        kind = check_bsdf_args(hits, dirs, rays, self._device, what)
+        buffer = hits.buffer if isinstance(hits, RayHits) else hits
+        n = int(buffer.shape[0])
+        p = _ffi.BsdfQueryParams()
+        p.count, p.mode = n, mode
+        if kind == "numpy":
+            if dirs.shape[1] == 3:
+                dirs = np.concatenate([dirs, np.zeros((n, 1), np.float32)], axis=1)
+            out = np.empty((n, 8), np.float32)
+            p.hits, p.dirs, p.out = buffer.ctypes.data, dirs.ctypes.data, out.ctypes.data
+            p.rays = rays.ctypes.data if rays is not None else None
+            self._check(self._lib.lrhip_query_bsdf(self._ctx, C.byref(p)))
+            return BsdfResults(out)
+        import torch
+        padded = dirs.shape[1] == 3
+        if padded:
+            dirs = torch.nn.functional.pad(dirs, (0, 1)).contiguous()
+        if sync or padded:  # (the padding copy runs on torch's stream, the query on the context's: the copy is waited for whatever `sync` says)
+            torch.cuda.current_stream(buffer.device).synchronize()
+        out = torch.empty((n, 8), dtype=torch.float32, device=buffer.device)
+        p.hits, p.dirs, p.out = buffer.data_ptr(), dirs.data_ptr(), out.data_ptr()
+        p.rays = rays.data_ptr() if rays is not None else None
+        p.flags = _ffi.RAY_DEVICE_POINTERS
+        self._check(self._lib.lrhip_query_bsdf(self._ctx, C.byref(p)))
+        if sync:
+            self.synchronize()
+        return BsdfResults(out)
+
+    def bsdf_evaluate(self, hits, wi, rays=None, sync: bool = True) -> BsdfResults:
+        """lrhip_query_bsdf, LRHIP_BSDF_EVALUATE (lrhip.h has the semantics): value and pdf of the closure at each hit for the direction wi --
+        float32 [N, 3] or [N, 4] (the fourth column is ignored), world space, pointing away from the surface, of any length.  hits: a RayHits
+        from trace(), or [N, 8] records the caller made; rays: the viewing rays (wo = -d / |d|), or None: wo = ng.  f includes |cos theta_i|.
+        numpy arrays go through host pointers; torch tensors on this renderer's GPU are read in place (an [N, 3] wi is padded by a copy) and
+        the result stays on the device (synchronisation as in trace())."""
+        return self._bsdf(_ffi.BSDF_EVALUATE, hits, wi, rays, sync, "wi")
+
+    def bsdf_sample(self, hits, u, rays=None, sync: bool = True) -> BsdfResults:
+        """lrhip_query_bsdf, LRHIP_BSDF_SAMPLE: a direction sampled from the closure at each hit with its value, pdf and event, from the three
+        random numbers u = (u_lobe, u_x, u_y) per record -- float32 [N, 3] or [N, 4].  The caller supplies them: no sampler is touched and the
+        result is a pure function of the arguments.  pdf = 0 marks a failed sample, whose f and wi may be non-finite: test pdf > 0 first.
+        Otherwise as bsdf_evaluate."""
+        return self._bsdf(_ffi.BSDF_SAMPLE, hits, u, rays, sync, "u")
+
+    def last_bsdf_ms(self) -> float:
+        """lrhip_last_bsdf_ms: HIP-event time of the kernel(s) of the last bsdf_evaluate() / bsdf_sample()"""
+        return float(self._lib.lrhip_last_bsdf_ms(self._ctx))
 
     def set_instance_transforms(self, matrices, instances=None, sync: bool = True) -> None:
         """lrhip_set_instance_transforms (lrhip.h has the semantics): move instances of the uploaded scene on the device -- their records, baked
