@@ -121,6 +121,9 @@ lrhip_surface_FLAGS = $(CALL_SAFE_FLAGS)
 # 1 - 2^-24, which leaves a pdf of 1e-8 where the reference has 0, and the cancellations of the visible-normal slope sampling (ggx_sample11)
 # turn last-bit differences of v_rcp / v_sqrt and of contraction into sampled directions 2e-3 away from the oracle's (measured)
 lrhip_bsdf_FLAGS = $(CALL_SAFE_FLAGS) -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-approx-func
+# lrhip_light.o holds the kernels of the light queries (csrc/hip/light_kernel.h): the texture lookup and the environment's evaluate / sample are
+# real calls, and a query hands ONE light sample to its caller, so it is built as lrhip_bsdf.o is, for the reason given there
+lrhip_light_FLAGS = $(lrhip_bsdf_FLAGS)
 $(HIP_OBJ): $(OBJDIR)/%.o: $(HIPDIR)/%.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $($*_FLAGS) -c -o $@ $<

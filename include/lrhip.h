@@ -21,6 +21,8 @@
  *   lrhip_query_surface            (no reference entry point: Geometry::shading_point, the closure's albedo / roughness and the light's emission
  *                                  at the caller's hits)
  *   lrhip_query_bsdf               (no reference entry point: Surface::Closure::evaluate / sample at the caller's hits)
+ *   lrhip_query_light              (no reference entry point: LightSampler::Instance::sample / evaluate_hit / evaluate_miss at the caller's hits,
+ *                                  DESIGN §4.15)
  *   lrhip_set_instance_transforms  (Geometry::update for matrices the caller holds, computed on the device)
  *   lrhip_set_mesh_vertices        (no reference equivalent: new vertex positions for one mesh, re-baked and refitted on the device)
  *   lrhip_get_counters             (no reference equivalent; roofline accounting)
@@ -351,7 +353,7 @@ double lrhip_last_surface_ms(lrhip_ctx *ctx);
  *                     misaligned device pointers and count > LRHIP_RAY_MAX_COUNT.
  *   Determinism       a record's result is a function of (record, ray, dirs, scene) only: bit-identical from run to run and wherever the record
  *                     stands in the batch.  lrhip_last_variant, film, AOV buffers and counters are untouched.
- *   Not done          nested Mix / Layered, importance transport, the closure's eta (Russian roulette), opacity, light sampling queries.     */
+ *   Not done          nested Mix / Layered, importance transport, the closure's eta (Russian roulette), opacity.                             */
 typedef struct lrhip_bsdf_result {            /* 32 bytes, two dwordx4 stores */
     float f[3];         float pdf;            /* value * |cos theta_i|; solid-angle density of wi */
     float wi[3];        uint32_t event;       /* unit world-space direction; LRHIP_BSDF_EVENT_* (evaluate: 0), LR_INVALID_ID in the invalid record */
@@ -374,6 +376,83 @@ typedef struct lrhip_bsdf_query_params {
 int lrhip_query_bsdf(lrhip_ctx *ctx, const lrhip_bsdf_query_params *params);
 /* HIP-event time of the kernel(s) of the last lrhip_query_bsdf call (a host-pointer call: summed over its chunks), in ms; synchronises */
 double lrhip_last_bsdf_ms(lrhip_ctx *ctx);
+
+/* Light queries: the scene's emitters as seen from points the caller names -- LightSampler::Instance::sample for three random
+ * numbers the caller gives (src/base/light_sampler.cpp:57-63, src/lightsamplers/uniform.cpp:78-137), or what a BSDF-sampled ray found at its
+ * end, LightSampler::Instance::evaluate_hit / evaluate_miss (uniform.cpp:50-76) -- the last piece of a next-event estimator of the caller's own:
+ * with lrhip_trace_rays, lrhip_query_surface and lrhip_query_bsdf, MegaPath's Li can be written as a loop over five queries.  Camera, integrator
+ * and sampler play no part: the query is a pure function of its inputs.
+ *   LRHIP_LIGHT_SAMPLE    one light, or the environment, sampled from each hit.
+ *     hits            resolved exactly as for lrhip_query_bsdf: hit.tri < the BVH's triangle count is the baked path, hit.tri == LR_INVALID_ID
+ *                     with valid (inst, prim) the instance path; every index is checked before it is used; a non-finite u or v gives the invalid
+ *                     record.  The hit need not carry a surface: the light sampler never asks for one.  No viewing ray is needed (rays is not
+ *                     read): the sampler reads the point, its normals and its offset bits, never wo.
+ *     dirs            one float4 per record: (u_light_selection, u_surface_x, u_surface_y, ignored) -- the three numbers the path tracer draws
+ *                     for its light sample, in its order; a non-finite one gives the invalid record.  No sampler is touched.
+ *     out_rays        lrhip_ray[count]: the shadow ray exactly as the shading block launches it -- the origin is the point moved off its surface
+ *                     towards the light (Interaction::p_robust), d the unit direction, t_min = 0, t_max = 0.9999 x the distance for an area
+ *                     light and FLT_MAX for the environment.  An array of its own, so that it goes into lrhip_trace_rays(LRHIP_RAY_ANY) as it
+ *                     stands.
+ *     out             L: the radiance towards the point.  pdf: the solid-angle density at the point TIMES the selection probability -- the
+ *                     shading block's light_pdf, so that balance(pdf, bsdf_pdf) / pdf is the reference's weight.  kind: LRHIP_LIGHT_KIND_AREA
+ *                     or LRHIP_LIGHT_KIND_ENVIRONMENT.  reserved is written 0.
+ *     A failed sample has pdf = 0 (the back of a one-sided light, a light seen at a grazing angle) and L = 0; its ray is whatever the sampler
+ *                     left there and may be non-finite: lrhip_trace_rays screens such rays.  Test pdf > 0 first, as the path tracer does.
+ *     LRHIP_LIGHT_FROM_POINTS (sample mode only): hits is float[4][count] = (p, ignored), a bare world-space point -- the reference's
+ *                     Interaction{p} of a medium point: no offset, the shadow ray starts at p itself.  Irradiance probes, volumes.  A non-finite
+ *                     p gives the invalid record.
+ *   LRHIP_LIGHT_EVALUATE  what a ray found.  rays (required) are the rays, hits the records lrhip_trace_rays wrote for them; dirs and out_rays are
+ *                     not read or written and may be NULL.
+ *     an emitter      a hit (resolved as above, back-facing by wo = -d / |d| under lrhip_query_surface's normalisation rule) on an instance with
+ *                     LR_SHAPE_HAS_LIGHT in a scene with lights: the light's L towards the ray's origin, pdf = its solid-angle density there x
+ *                     (1 - env_prob) / light_count, kind = LRHIP_LIGHT_KIND_AREA (src/integrators/mega_path.cpp:79-86).  From behind a one-sided
+ *                     light: L = 0, pdf = 0, still LRHIP_LIGHT_KIND_AREA.
+ *     a miss          exactly what lrhip_trace_rays writes, inst == tri == LR_INVALID_ID, in a scene with an environment: the environment's L
+ *                     along d / |d|, pdf x env_prob, kind = LRHIP_LIGHT_KIND_ENVIRONMENT (mega_path.cpp:70-76).
+ *     anything else   a hit on a non-emitter, a miss in a scene without an environment: L = 0, pdf = 0, kind = LRHIP_LIGHT_KIND_NONE -- a valid answer.
+ *   THE INVALID RECORD    an all-zero ray (sample mode; the ray queries screen a zero direction) and an all-zero result except kind =
+ *                     LR_INVALID_ID: in sample mode a miss, an id out of range, a non-finite u, v, dirs or point; in evaluate mode a ray
+ *                     lrhip_trace_rays would screen, a non-finite u or v, an id out of range that is not the miss pattern.  A malformed record
+ *                     never faults.
+ *   No lighting       a scene with neither lights nor an environment is no error: every record, whatever it holds, is answered L = 0, pdf = 0,
+ *                     kind = LRHIP_LIGHT_KIND_NONE, with a zero ray in sample mode, and no light table is read.
+ *   Scope             scenes of every integrator and every closure set, Mix / Layered surfaces nested in each other included: no closure is
+ *                     touched.  Spherical (constant or image), Directional and Combined environments, Combined nodes nested in each other included.
+ *   Pointers          as for lrhip_query_bsdf.  With LRHIP_RAY_DEVICE_POINTERS every array is device memory, 16-byte aligned (else
+ *                     LRHIP_ERROR_INVALID), and the call is asynchronous on the context's stream: trace, sample, trace the shadow rays needs no
+ *                     host round trip.  Without it they are host memory, staged 2^20 records at a time through context-owned buffers released
+ *                     with the context, and the call synchronises.
+ *   Errors            LRHIP_ERROR_INVALID before any upload, with count > 0 for NULL hits or out, NULL dirs or out_rays in sample mode and NULL
+ *                     rays in evaluate mode, for unknown flags, an unknown mode, LRHIP_LIGHT_FROM_POINTS in evaluate mode, misaligned device
+ *                     pointers and count > LRHIP_RAY_MAX_COUNT.
+ *   Determinism       a record's result is a function of (record, ray, dirs, scene) only: bit-identical from run to run and wherever the record
+ *                     stands in the batch.  The tables are read as lrhip_update_scene, lrhip_set_instance_transforms and
+ *                     lrhip_set_mesh_vertices left them.  lrhip_last_variant, film, AOV buffers and counters are untouched.
+ *   Not done          which light or triangle a sample picked, beyond kind; power- or BVH-based light selection; emitter sampling for media
+ *                     transmittance.                                                                                                        */
+typedef struct lrhip_light_result {           /* 32 bytes, two dwordx4 stores */
+    float L[3];         float pdf;            /* radiance towards the point; solid-angle density x selection probability */
+    uint32_t kind;      uint32_t reserved[3]; /* LRHIP_LIGHT_KIND_*, LR_INVALID_ID in the invalid record; 0 */
+} lrhip_light_result;
+#define LRHIP_LIGHT_SAMPLE 0u
+#define LRHIP_LIGHT_EVALUATE 1u
+#define LRHIP_LIGHT_KIND_AREA 0u
+#define LRHIP_LIGHT_KIND_ENVIRONMENT 1u
+#define LRHIP_LIGHT_KIND_NONE 2u
+#define LRHIP_LIGHT_FROM_POINTS 64u
+typedef struct lrhip_light_query_params {
+    const void *hits;   /* lrhip_ray_hit[count]; with LRHIP_LIGHT_FROM_POINTS float[4][count] = (p, -) */
+    const void *rays;   /* LRHIP_LIGHT_EVALUATE: lrhip_ray[count]; LRHIP_LIGHT_SAMPLE: not read */
+    const void *dirs;   /* LRHIP_LIGHT_SAMPLE: float[4][count] = (u_light_selection, u_surface_x, u_surface_y, -); LRHIP_LIGHT_EVALUATE: not read */
+    void *out_rays;     /* LRHIP_LIGHT_SAMPLE: lrhip_ray[count], the shadow rays; LRHIP_LIGHT_EVALUATE: not written */
+    void *out;          /* lrhip_light_result[count] */
+    uint64_t count;     /* 0 is legal and launches nothing; at most LRHIP_RAY_MAX_COUNT */
+    uint32_t mode;      /* LRHIP_LIGHT_SAMPLE or LRHIP_LIGHT_EVALUATE */
+    uint32_t flags;     /* LRHIP_RAY_DEVICE_POINTERS, LRHIP_LIGHT_FROM_POINTS */
+} lrhip_light_query_params;
+int lrhip_query_light(lrhip_ctx *ctx, const lrhip_light_query_params *params);
+/* HIP-event time of the kernel(s) of the last lrhip_query_light call (a host-pointer call: summed over its chunks), in ms; synchronises */
+double lrhip_last_light_ms(lrhip_ctx *ctx);
 
 /* Moving instances on the device: Geometry::update (src/base/geometry.cpp:194-216) for object-to-world matrices the caller holds --
  * an animation frame, a physics step whose matrices are a tensor on the GPU, a drag in an editor -- between two renders or queries, without a

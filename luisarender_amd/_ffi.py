@@ -180,6 +180,17 @@ class BsdfQueryParams(C.Structure):
                 ("flags", u32)]
 
 
+class LightResult(C.Structure):
+    """lrhip_light_result (include/lrhip.h): one row of the [N, 8] 32-bit buffer behind LightSamples / LightResults"""
+    _fields_ = [("L", f32 * 3), ("pdf", f32), ("kind", u32), ("reserved", u32 * 3)]
+
+
+class LightQueryParams(C.Structure):
+    """lrhip_light_query_params (include/lrhip.h)"""
+    _fields_ = [("hits", C.c_void_p), ("rays", C.c_void_p), ("dirs", C.c_void_p), ("out_rays", C.c_void_p), ("out", C.c_void_p), ("count", u64),
+                ("mode", u32), ("flags", u32)]
+
+
 class InstanceUpdateParams(C.Structure):
     """lrhip_instance_update_params (include/lrhip.h)"""
     _fields_ = [("object_to_world", C.c_void_p), ("instances", C.c_void_p), ("count", u64), ("flags", u32)]
@@ -205,9 +216,14 @@ SURFACE_VALID, SURFACE_BACK_FACING, SURFACE_HAS_SURFACE, SURFACE_HAS_LIGHT = 1, 
 BSDF_EVALUATE, BSDF_SAMPLE = 0, 1  # lrhip_bsdf_query_params::mode: LRHIP_BSDF_EVALUATE / LRHIP_BSDF_SAMPLE
 # lrhip_bsdf_result::event: LRHIP_BSDF_EVENT_REFLECT / ENTER / EXIT / THROUGH (LR_INVALID_ID in the invalid record)
 BSDF_EVENT_REFLECT, BSDF_EVENT_ENTER, BSDF_EVENT_EXIT, BSDF_EVENT_THROUGH = 0, 1, 2, 4
+LIGHT_SAMPLE, LIGHT_EVALUATE = 0, 1  # lrhip_light_query_params::mode: LRHIP_LIGHT_SAMPLE / LRHIP_LIGHT_EVALUATE
+LIGHT_FROM_POINTS = 64  # LRHIP_LIGHT_FROM_POINTS
+# lrhip_light_result::kind: LRHIP_LIGHT_KIND_AREA / ENVIRONMENT / NONE (LR_INVALID_ID in the invalid record)
+LIGHT_KIND_AREA, LIGHT_KIND_ENVIRONMENT, LIGHT_KIND_NONE = 0, 1, 2
 
 STRUCTS = {"lrhip_surface_point": SurfacePoint, "lrhip_surface_query_params": SurfaceQueryParams,
 "lrhip_bsdf_result": BsdfResult, "lrhip_bsdf_query_params": BsdfQueryParams,
+"lrhip_light_result": LightResult, "lrhip_light_query_params": LightQueryParams,
 "lrhip_denoise_params": DenoiseParams, "lrhip_ray": Ray, "lrhip_ray_hit": RayHit, "lrhip_ray_query_params": RayQueryParams,
            "lrhip_radiance_query_params": RadianceQueryParams, "lrhip_instance_update_params": InstanceUpdateParams,
            "lrhip_mesh_update_params": MeshUpdateParams,
@@ -334,6 +350,9 @@ def hip_lib(path: str | None = None) -> C.CDLL:
         lib.lrhip_query_bsdf.argtypes = [C.c_void_p, C.POINTER(BsdfQueryParams)]
         lib.lrhip_last_bsdf_ms.restype = C.c_double
         lib.lrhip_last_bsdf_ms.argtypes = [C.c_void_p]
+        lib.lrhip_query_light.argtypes = [C.c_void_p, C.POINTER(LightQueryParams)]
+        lib.lrhip_last_light_ms.restype = C.c_double
+        lib.lrhip_last_light_ms.argtypes = [C.c_void_p]
         lib.lrhip_set_instance_transforms.argtypes = [C.c_void_p, C.POINTER(InstanceUpdateParams)]
         lib.lrhip_last_instance_update_ms.restype = C.c_double
         lib.lrhip_last_instance_update_ms.argtypes = [C.c_void_p]

@@ -972,7 +972,7 @@ LR_CALL EnvSample env_sample_one(EnvTables tb, const DEnvironment *envp, f2 u) {
 // explicit stack, in the reference's operation order (post-order: a.L * scale_a + b.L * scale_b, the pdfs interpolated), by out-of-line
 // functions that only the variants which make real calls anyway hold (lrhip_kernels.hip picks one for such a scene) -- the lean kernels' register
 // allocation never sees them.  At most LR_ENV_MAX_COMBINED_DEPTH Combined nodes on a path (lr_scene.h; checked at upload).
-#if defined(LR_VARIANT) && ((LR_VARIANT) & (96 | 256))
+#if (defined(LR_VARIANT) && ((LR_VARIANT) & (96 | 256))) || defined(LR_ENV_TREE_WALK)// (LR_ENV_TREE_WALK: lrhip_light.hip, the light queries)
 #define LR_ENV_TREE 1
 __device__ __noinline__ EnvEval env_evaluate_tree(EnvTables tb, const DEnvironment *root, f3 wi) {// CombinedInstance::evaluate, combined.cpp:57-78
     const DEnvironment *node[LR_ENV_MAX_COMBINED_DEPTH];

@@ -138,6 +138,9 @@ void lrhip_destroy(lrhip_ctx *ctx) {
     ctx->bsdf_dirs.release(), ctx->bsdf_out.release();
     if (ctx->bsdf_begin) { (void)hipEventDestroy(ctx->bsdf_begin); }
     if (ctx->bsdf_end) { (void)hipEventDestroy(ctx->bsdf_end); }
+    ctx->light_rays.release(), ctx->light_out.release();
+    if (ctx->light_begin) { (void)hipEventDestroy(ctx->light_begin); }
+    if (ctx->light_end) { (void)hipEventDestroy(ctx->light_end); }
     ctx->spill.release(), ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->wf_counts.release(), ctx->wf_accum.release();
     ctx->pool.release(), ctx->counters.release(), ctx->work_counter.release(), ctx->scene_record.release();
     if (ctx->ev_begin) { (void)hipEventDestroy(ctx->ev_begin); }

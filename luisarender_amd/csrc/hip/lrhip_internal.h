@@ -12,6 +12,7 @@
 //   lrhip_radiance.hip   radiance queries: MegaPath's estimator along caller-supplied rays (the kFeatQuery kernels of megapath_kernel.h)
 //   lrhip_surface.hip    surface queries: position, normals, uv, material and emission at caller-supplied hits (surface_kernel.h)
 //   lrhip_bsdf.hip       BSDF queries: the closure evaluated or sampled at caller-supplied hits (bsdf_kernel.h)
+//   lrhip_light.hip      light queries: the emitters sampled from, or evaluated at, caller-supplied hits (light_kernel.h)
 //   lrhip_instance_update.hip  moving instances on the device: re-bake, refit and re-quantise (instance_update_kernels.h); the table test hook
 //   lrhip_mesh_update.hip      deforming a mesh on the device: vertex write, normal recompute, marking (mesh_update_kernels.h), then the re-bake and refit
 // Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
@@ -223,6 +224,14 @@ struct lrhip_ctx {
     hipEvent_t bsdf_begin{nullptr}, bsdf_end{nullptr};
     double bsdf_ms{0.};
     bool bsdf_pending{false};
+    // light queries (lrhip_light.hip).  Of the context: the staging buffers of a host-pointer call's results (shadow rays, records; hit records or
+    // points go through surface_hits, the rays through raycast_rays, the random numbers through bsdf_dirs) -- they grow on demand and
+    // outlive the scene --, the events around the last launch, the kernel time of the last call's finished launches and whether one is
+    // still to be read (lrhip_last_light_ms).  The lr_mesh table is the surface queries' (surface_meshes)
+    lrh::DeviceBuffer light_rays, light_out;
+    hipEvent_t light_begin{nullptr}, light_end{nullptr};
+    double light_ms{0.};
+    bool light_pending{false};
 };
 
 namespace lrh {

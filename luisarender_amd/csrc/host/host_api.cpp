@@ -176,6 +176,7 @@ uint64_t lrhost_sizeof(const char *name) {
     LR_SIZEOF(lrhip_instance_update_params) LR_SIZEOF(lrhip_mesh_update_params)
     LR_SIZEOF(lrhip_surface_point) LR_SIZEOF(lrhip_surface_query_params)
     LR_SIZEOF(lrhip_bsdf_result) LR_SIZEOF(lrhip_bsdf_query_params)
+    LR_SIZEOF(lrhip_light_result) LR_SIZEOF(lrhip_light_query_params)
 #undef LR_SIZEOF
     return 0u;
 }

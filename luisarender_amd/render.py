@@ -166,6 +166,73 @@ def check_bsdf_args(hits, dirs, rays=None, device: int | None = None, what: str 
     return kind
 
 
+def check_light_args(hits=None, u=None, points=None, rays=None, device: int | None = None, mode: str = "sample") -> str:
+    """What MegaPathRenderer.light_sample (mode "sample") / light_evaluate (mode "evaluate") accept (no device needed).
+    sample: exactly one of hits -- a RayHits, or a float32 [N, 8] array of lrhip_ray_hit records, as check_surface_args takes them -- and
+    points -- float32 [N, 3] or [N, 4] world-space positions; u: float32 [N, 3] or [N, 4], (u_light_selection, u_surface_x, u_surface_y);
+    rays must be None.  An [N, 4] array must be contiguous (it is read in place), an [N, 3] one is padded by a copy.
+    evaluate: hits and rays, as check_surface_args takes them; u and points must be None.
+    All are of one kind (numpy, or torch on one GPU) and have the same N.  Returns check_rays' answer; TypeError for an argument that is no
+    array or tensor at all, ValueError for anything else."""
+    def is_array(a):
+        return isinstance(a, np.ndarray) or (type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr"))
+
+    if mode not in ("sample", "evaluate"):
+        raise ValueError(f"light: unknown mode {mode!r}")
+    buffer = hits.buffer if isinstance(hits, RayHits) else hits
+    for name, a in (("hits", buffer), ("u", u), ("points", points), ("rays", rays)):
+        if a is not None and not is_array(a):
+            raise TypeError(f"light: {name} must be a numpy array or a torch tensor, not {type(a).__name__}")
+    if mode == "evaluate":
+        if u is not None or points is not None:
+            raise ValueError("light: light_evaluate takes hits and rays, neither u nor points")
+        if hits is None or rays is None:
+            raise ValueError("light: light_evaluate needs both the hits and the rays that found them")
+        return check_surface_args(hits, rays, device, prefix="light")
+    if rays is not None:
+        raise ValueError("light: light_sample reads no viewing rays")
+    if (hits is None) == (points is None):
+        raise ValueError("light: light_sample takes hits or points, one of them")
+    if u is None:
+        raise ValueError("light: light_sample needs u")
+
+    def check_rows(name, a, like):
+        # a float32 [N, 3] or [N, 4] array of `like`'s kind (and device); returns its kind
+        if isinstance(a, np.ndarray):
+            kind, is_float32, contiguous = "numpy", a.dtype == np.float32, a.flags["C_CONTIGUOUS"]
+        else:
+            import torch
+            kind, is_float32, contiguous = "torch", a.dtype == torch.float32, a.is_contiguous()
+            if a.device.type != "cuda":
+                raise ValueError(f"light: the {name} tensor is on {a.device}, not on a GPU")
+            if device is not None and a.device.index != device:
+                raise ValueError(f"light: the {name} tensor is on {a.device}, the renderer on GPU {device}")
+        if like is not None:
+            like_kind = "numpy" if isinstance(like, np.ndarray) else "torch"
+            if kind != like_kind:
+                raise ValueError(f"light: {name} is a {kind} array, the records a {like_kind} array")
+            if kind == "torch" and a.device != like.device:
+                raise ValueError(f"light: {name} is on {a.device}, the records on {like.device}")
+        if not is_float32:
+            raise ValueError(f"light: {name} must be float32, not {a.dtype}")
+        if a.ndim != 2 or a.shape[1] not in (3, 4):
+            raise ValueError(f"light: {name} must have shape [N, 3] or [N, 4], not {tuple(a.shape)}")
+        if a.shape[1] == 4 and not contiguous:
+            raise ValueError(f"light: an [N, 4] {name} is read in place and must be contiguous")
+        return kind
+
+    if points is not None:
+        kind = check_rows("points", points, None)
+        records = points
+    else:
+        kind = check_surface_args(hits, None, device, prefix="light")
+        records = buffer
+    check_rows("u", u, records)
+    if int(u.shape[0]) != int(records.shape[0]):
+        raise ValueError(f"light: {int(records.shape[0])} records for {int(u.shape[0])} rows of u")
+    return kind
+
+
 def check_instance_transforms(matrices, instances=None, instance_count: int | None = None, device: int | None = None) -> str:
     """What MegaPathRenderer.set_instance_transforms and Scene.set_instance_transforms accept (no device needed).  matrices: float32,
     contiguous, [N, 4, 4] or [N, 16] in COLUMN-MAJOR storage -- matrices[i, c, r] (flat: [i, 4 c + r]) is row r of column c, the layout of
@@ -364,6 +431,37 @@ class BsdfResults:
 
     def __len__(self) -> int:
         return int(self.buffer.shape[0])
+
+
+class LightResults:
+    """Results of MegaPathRenderer.light_evaluate: views (no copies) of ONE [N, 8] 32-bit buffer of lrhip_light_result records -- `buffer`, a
+    float32 numpy array or, for the torch path, the float32 tensor on the device.  L: [N, 3]; pdf: [N], the solid-angle density times the
+    selection probability; kind: uint32 (torch: int32, LR_INVALID_ID reads -1), _ffi.LIGHT_KIND_*; valid: bool, false for the invalid record."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        if isinstance(buffer, np.ndarray):
+            ids = buffer.view(np.uint32)
+        else:
+            import torch
+            ids = buffer.view(torch.int32)
+        self.L, self.pdf, self.kind = buffer[:, 0:3], buffer[:, 3], ids[:, 4]
+
+    @property
+    def valid(self):
+        return self.kind != (0xFFFFFFFF if isinstance(self.buffer, np.ndarray) else -1)
+
+    def __len__(self) -> int:
+        return int(self.buffer.shape[0])
+
+
+class LightSamples(LightResults):
+    """Results of MegaPathRenderer.light_sample: LightResults, and `rays`, the [N, 8] float32 buffer of shadow rays (ox, oy, oz, 0, dx, dy,
+    dz, t_max) that trace(rays, any_hit=True) takes as it stands.  pdf = 0 marks a failed sample, whose ray may be non-finite."""
+
+    def __init__(self, rays, buffer):
+        super().__init__(buffer)
+        self.rays = rays
 
 
 class MegaPathRenderer:
@@ -649,6 +747,76 @@ class MegaPathRenderer:
     def last_bsdf_ms(self) -> float:
         """lrhip_last_bsdf_ms: HIP-event time of the kernel(s) of the last bsdf_evaluate() / bsdf_sample()"""
         return float(self._lib.lrhip_last_bsdf_ms(self._ctx))
+
+    def light_sample(self, hits=None, u=None, points=None, sync: bool = True) -> LightSamples:
+        """lrhip_query_light, LRHIP_LIGHT_SAMPLE (lrhip.h has the semantics): one light or the environment sampled from each hit -- a RayHits
+        from trace(), or [N, 8] records the caller made -- or, with points instead of hits, from bare world-space positions [N, 3] or [N, 4]
+        (LRHIP_LIGHT_FROM_POINTS: no offset off a surface), with the three random numbers u = (u_light_selection, u_surface_x, u_surface_y) per
+        record, float32 [N, 3] or [N, 4].  Returns LightSamples: the shadow rays, ready for trace(rays, any_hit=True), L, and pdf, which
+        includes the selection probability; pdf = 0 marks a failed sample.  numpy arrays go through host pointers; torch tensors on this
+        renderer's GPU are read in place (an [N, 3] array is padded by a copy) and the results stay on the device (synchronisation as in
+        trace())."""
+        kind = check_light_args(hits, u, points, None, self._device, "sample")
+        records = points if points is not None else (hits.buffer if isinstance(hits, RayHits) else hits)
+        n = int(records.shape[0])
+        p = _ffi.LightQueryParams()
+        p.count, p.mode = n, _ffi.LIGHT_SAMPLE
+        p.flags = _ffi.LIGHT_FROM_POINTS if points is not None else 0
+        if kind == "numpy":
+            pad = lambda a: np.concatenate([a, np.zeros((n, 1), np.float32)], axis=1) if a.shape[1] == 3 else a  # noqa: E731
+            u = pad(u)
+            if points is not None:
+                records = pad(records)
+            rays, out = np.empty((n, 8), np.float32), np.empty((n, 8), np.float32)
+            p.hits, p.dirs, p.out_rays, p.out = records.ctypes.data, u.ctypes.data, rays.ctypes.data, out.ctypes.data
+            self._check(self._lib.lrhip_query_light(self._ctx, C.byref(p)))
+            return LightSamples(rays, out)
+        import torch
+        padded = u.shape[1] == 3 or (points is not None and records.shape[1] == 3)
+        pad = lambda a: torch.nn.functional.pad(a, (0, 1)).contiguous() if a.shape[1] == 3 else a  # noqa: E731
+        u = pad(u)
+        if points is not None:
+            records = pad(records)
+        if sync or padded:  # (the padding copy runs on torch's stream, the query on the context's: the copy is waited for whatever `sync` says)
+            torch.cuda.current_stream(records.device).synchronize()
+        rays = torch.empty((n, 8), dtype=torch.float32, device=records.device)
+        out = torch.empty((n, 8), dtype=torch.float32, device=records.device)
+        p.hits, p.dirs, p.out_rays, p.out = records.data_ptr(), u.data_ptr(), rays.data_ptr(), out.data_ptr()
+        p.flags |= _ffi.RAY_DEVICE_POINTERS
+        self._check(self._lib.lrhip_query_light(self._ctx, C.byref(p)))
+        if sync:
+            self.synchronize()
+        return LightSamples(rays, out)
+
+    def light_evaluate(self, hits, rays, sync: bool = True) -> LightResults:
+        """lrhip_query_light, LRHIP_LIGHT_EVALUATE: what each ray found at its end -- hits are the records trace(rays) wrote.  A hit on an
+        emitter gives its L towards the ray's origin and the pdf light_sample would have had for that point (kind _ffi.LIGHT_KIND_AREA), a miss
+        the environment's (LIGHT_KIND_ENVIRONMENT), anything else L = 0, pdf = 0 (LIGHT_KIND_NONE): what a path tracer weighs a BSDF-sampled
+        ray's emission with.  Otherwise as light_sample."""
+        kind = check_light_args(hits, None, None, rays, self._device, "evaluate")
+        buffer = hits.buffer if isinstance(hits, RayHits) else hits
+        n = int(buffer.shape[0])
+        p = _ffi.LightQueryParams()
+        p.count, p.mode = n, _ffi.LIGHT_EVALUATE
+        if kind == "numpy":
+            out = np.empty((n, 8), np.float32)
+            p.hits, p.rays, p.out = buffer.ctypes.data, rays.ctypes.data, out.ctypes.data
+            self._check(self._lib.lrhip_query_light(self._ctx, C.byref(p)))
+            return LightResults(out)
+        import torch
+        if sync:
+            torch.cuda.current_stream(buffer.device).synchronize()
+        out = torch.empty((n, 8), dtype=torch.float32, device=buffer.device)
+        p.hits, p.rays, p.out = buffer.data_ptr(), rays.data_ptr(), out.data_ptr()
+        p.flags = _ffi.RAY_DEVICE_POINTERS
+        self._check(self._lib.lrhip_query_light(self._ctx, C.byref(p)))
+        if sync:
+            self.synchronize()
+        return LightResults(out)
+
+    def last_light_ms(self) -> float:
+        """lrhip_last_light_ms: HIP-event time of the kernel(s) of the last light_sample() / light_evaluate()"""
+        return float(self._lib.lrhip_last_light_ms(self._ctx))
 
     def set_instance_transforms(self, matrices, instances=None, sync: bool = True) -> None:
         """lrhip_set_instance_transforms (lrhip.h has the semantics): move instances of the uploaded scene on the device -- their records, baked
