@@ -31,8 +31,8 @@ HOST_HDR := $(wildcard $(HOSTDIR)/*.h) $(wildcard include/*.h)
 HIP_SRC := $(wildcard $(HIPDIR)/lrhip_*.hip)
 HIP_HDR := $(wildcard $(HIPDIR)/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly nopair noride
-all: host oracle hip cli ieee shallow noearly nopair noride
+.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly nopair noride nostraight
+all: host oracle hip cli ieee shallow noearly nopair noride nostraight
 
 # oracle/_ref: the reference's OWN sources compiled in place against the scalar LuisaCompute stand-in of oracle/ref_shim
 # (test infrastructure: pins oracle/ to the reference; needs /root/reference, so only where the reference tree exists)
@@ -178,6 +178,17 @@ $(LIBDIR)/variants/liblrhip_nopair.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip
 noride: $(LIBDIR)/variants/liblrhip_noride.so
 $(LIBDIR)/variants/liblrhip_noride.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
 	$(MAKE) --no-print-directory hip-variant NAME=noride DEFS='-DLR_POOL_SHADOW_RIDE=0' VARIANT_MASKS='4096 4097 4098 4099 4100 4101 4102 4103 4116 4117 20482 20483 12308 12309' HEAVY_MASKS=
+
+# Kernels once more WITHOUT the straight-line control flow of the traversal loop (dev_trace.h: LR_STRAIGHT_TAIL): the three pushes of a node step are
+# EXEC regions again and a closest hit is committed by selects on VCC.  The lean one-path kernels and every pool kernel but the continuation passes
+# take the shipped form; this library holds the kernels <0> / <1> and the pool kernels that the suite's scenes and the benchmark's configurations
+# select (the masks of `noride`).  TEST INFRASTRUCTURE: the shipped form lays an iteration's instructions
+# out differently and nothing else, so the shipped library's frames and its path / ray / node / triangle counters must equal this
+# library's (tests/test_gpu_straight_tail.py).  `make shallow` is built WITH the shipped form: the same test holds its pool kernel, whose node steps
+# stand at the boundary to the overflow area, to the shipped film.
+nostraight: $(LIBDIR)/variants/liblrhip_nostraight.so
+$(LIBDIR)/variants/liblrhip_nostraight.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
+	$(MAKE) --no-print-directory hip-variant NAME=nostraight DEFS='-DLR_STRAIGHT_TAIL=0' VARIANT_MASKS='0 1 4096 4097 4098 4099 4100 4101 4102 4103 4116 4117 20482 20483 12308 12309' HEAVY_MASKS=
 
 cli: $(BINDIR)/luisa-render-cli
 $(BINDIR)/luisa-render-cli: $(HOSTDIR)/cli.cpp $(HOSTDIR)/plugin_megapath.cpp $(LIBDIR)/liblrhost.so $(HOST_HDR)

@@ -404,13 +404,60 @@ LR_D void trav_packets_done() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
+// LR_STRAIGHT_TAIL: THE ITERATION'S CONTROL FLOW, STRAIGHTENED.  The loop is issue-bound and a wave's scalar and branch instructions cost it issue
+// slots like its vector ones; of the 426 instructions of a pool iteration 151 were control flow and bookkeeping.  Two bits, 0 = the former code:
+//   1  the three pushes of a node step are stores at the top of the stack without EXEC regions (trav_node_tail<false, true>): 6 VALU instructions and
+//      3 stores where the regions held three v_cmp / s_and_saveexec / s_cbranch / v_add / s_waitcnt / ds_write / s_or, threaded through shared
+//      blocks with taken branches;
+//   2  pool kernels without the alpha test: the three words of a closest hit are VOP3 selects on a mask in scalar registers instead of
+//      v_cndmask_b32_e32 back to back on one VCC (trav_leaf_test; ctx_start: 18.7 cycles each in that form).
+// Same walk, same wave iterations, same arithmetic: films and the path, ray, node and triangle counters are bit-identical (tests/test_gpu_straight_tail.py,
+// against `make nostraight`), and so are the lane-iterations where they are a function of the binary: with one work item per tile (under the default
+// partition a few waves get a second item, by a race, and the counter scatters by 0.02 % between two launches of ONE library).  Against the commit
+// before, three bench runs a side: C2 1288.0 -> 1310.5 Msamples/s (+ 1.75 %, a side's runs
+// 0.15 % apart), C3 1276 -> 1293, C4 1579 -> 1594, PaddedSobol-C2 1202 -> 1222, C5 644.1 -> 649.1; the loop's range in the census 516 -> 484 instructions.
+// The forms one by one, C2, same box, builds alternating, Msamples/s (profiles/straight_tail_ab.txt): the former code 1285.2 / 1285.3, bit 1
+// 1308.1 / 1308.1 (+ 1.8 %); bit 2 on top of bit 1 and the cold `deep` copy below: 1313.4 -> 1317.7 (+ 0.3 %); bit 1 in the serial flow: C1 <0> 5446 ->
+// 5499 (+ 1.0 %), C5 <5240> 645.0 -> 650.6 (+ 0.9 %).  <4096> stays at 128 VGPRs without a spill.
+// WHERE: the lean one-path kernels (masks 0 - 15) and the pool kernels but the continuation passes of wavefront mode -- no kernel of these spills more
+// than before.  Everywhere else the allocation sits at its limit and answers any change of the loop with a few spilled VGPRs more in a counting twin
+// (<61> 399 -> 404, <253> 495 -> 502, <1029> 167 -> 168, <7169> 154 -> 157, <7183> 208 -> 210): those families keep the former code, byte for byte.
+// MEASURED, NOT KEPT:
+//   * the `deep` iteration as a copy of its own behind one branch that is not expected, so that the common iteration holds no `deep` form and its pop,
+//     node step and tail fall through (they are reached by s_cbranch_vccnz to a far block and s_branch back): C2 1308.1 -> 1313.9 (+ 0.45 %), but the
+//     second copy of the iteration costs registers where the shading block needs them -- <4097> 100 -> 125 spilled VGPRs, <5120> 21 -> 38, <4116> 60 -> 70;
+//     __builtin_expect on the vote alone moves no block;
+//   * the hit as MOVES UNDER EXEC, pinned as ctx_start's are (one region for a closest hit's three words, one for `occluded` and the stack drop of a
+//     shadow ray: five moves, seven scalar instructions, two branches): C2 1308.1 -> 1299.2, it LOSES 0.7 %;
+//   * the step of a push as a select on the key's sign: the stride in a VGPR of its own, <4096> spills two (not run).
+#ifndef LR_STRAIGHT_TAIL
+#if defined(LR_VARIANT) && ((((LR_VARIANT) & 4096) && !((LR_VARIANT) & 2048)) || ((LR_VARIANT) & ~15) == 0)
+#define LR_STRAIGHT_TAIL 3
+#else
+#define LR_STRAIGHT_TAIL 0
+#endif
+#endif
 // the pushes / pop of a node step: far -> near so that the nearest is popped first; the nearest stays in `cur`
-template<bool D>
+template<bool D, bool STRAIGHT = false>
 LR_D void trav_node_tail(const TraversalStack &stack, const TravLane &tl, TravState &tr, uint32_t &spb, const uint32_t (&key)[4], uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3) {
     // (a lane that hit nothing pushes nothing: its pop goes out with the reference reads, not behind the pushes -- round 5: +0.8 % on the
     // one-path kernel, +1.2 % on the Cornell box)
     auto popped = kInvalid;
     if (static_cast<int>(key[0]) < 0) { popped = trav_pop(stack, tl, spb, D); }
+    if constexpr (!D && STRAIGHT) {
+        // STRAIGHT-LINE PUSHES.  Every reference is stored at the top of the stack, and the top advances only behind a valid one.  The keys are
+        // sorted, so the valid ones are a prefix: a store for a missed child leaves a word ABOVE the top, which the next store of this lane
+        // overwrites (a wave's LDS operations complete in order) or which stays there, dead.  Not `deep`: sp + 3 <= kStackLds for every lane of
+        // the wave, so all three addresses lie in the lane's own LDS rows whatever the keys are; the pop above went out before them.
+        // (the step is min(~key, stride): ~kInvalid is 0, the complement of a valid key -- a non-negative float's bits -- is at least 2^31.  As a
+        // select on the key's sign it wanted the stride in a VGPR of its own -- a VOP3 select reads VCC and no second scalar -- and <4096> spilled two)
+        const auto step = [](uint32_t k) { return min(~k, kStackStride); };
+        spb_store(spb, r3), spb += step(key[3]);
+        spb_store(spb, r2), spb += step(key[2]);
+        spb_store(spb, r1), spb += step(key[1]);
+        tr.cur = static_cast<int>(key[0]) >= 0 ? r0 : popped;
+        return;
+    }
     if (static_cast<int>(key[3]) >= 0) { trav_push(stack, tl, spb, r3, D); }
     if (static_cast<int>(key[2]) >= 0) { trav_push(stack, tl, spb, r2, D); }
     if (static_cast<int>(key[1]) >= 0) { trav_push(stack, tl, spb, r1, D); }
@@ -420,6 +467,7 @@ template<bool COUNT, bool FETCHED = false>
 LR_D void trav_node_step(const TraversalStack &stack, const TravLane &tl, TravState &tr, uint32_t &spb, f3 inv, bool is_inner, bool deep, TraceStats &stats) {
     typedef __attribute__((address_space(3))) void lds_void;
     typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
+    constexpr bool STRAIGHT = (LR_STRAIGHT_TAIL & 1) != 0;
     if (!FETCHED) {
         prio_chain();
         trav_node_fetch(stack, tl, tr, is_inner);
@@ -445,7 +493,7 @@ LR_D void trav_node_step(const TraversalStack &stack, const TravLane &tl, TravSt
             prio_chain();
             const auto r0 = ref_of(key[0]), r1 = ref_of(key[1]), r2 = ref_of(key[2]), r3 = ref_of(key[3]);
             if (deep) { trav_node_tail<true>(stack, tl, tr, spb, key, r0, r1, r2, r3); }
-            else { trav_node_tail<false>(stack, tl, tr, spb, key, r0, r1, r2, r3); }
+            else { trav_node_tail<false, STRAIGHT>(stack, tl, tr, spb, key, r0, r1, r2, r3); }
         }
         trav_packets_done();
         LR_MARK(kProbeChain, tr.cur, spb);
@@ -465,7 +513,7 @@ LR_D void trav_node_step(const TraversalStack &stack, const TravLane &tl, TravSt
         // harmless); round 5, with the loop lighter: +0.5 % on both kernel families, profiles/r05r_refs_batched_turnover.txt
         const auto r0 = ref_of(key[0]), r1 = ref_of(key[1]), r2 = ref_of(key[2]), r3 = ref_of(key[3]);
         if (deep) { trav_node_tail<true>(stack, tl, tr, spb, key, r0, r1, r2, r3); }
-        else { trav_node_tail<false>(stack, tl, tr, spb, key, r0, r1, r2, r3); }
+        else { trav_node_tail<false, STRAIGHT>(stack, tl, tr, spb, key, r0, r1, r2, r3); }
 #ifndef LR_TRACE_PROBE
         if (COUNT && key[0] == kInvalid) { stats.nodes_empty++; }
 #endif
@@ -585,6 +633,20 @@ LR_D bool trav_leaf_test(TravState &tr, uint32_t ref, const LeafTriangle &tri, T
         // (a lane at a leaf traces a shadow ray or a closest-hit ray -- kPhaseShadow / kPhaseClosest, nothing else where no alpha test parks candidates:
         // ONE compare serves both uses of the phase)
         const auto shadow = tr.phase == kPhaseShadow;
+        if constexpr ((LR_STRAIGHT_TAIL & 2) != 0) {
+            // (LR_STRAIGHT_TAIL bit 2: a closest hit's words as VOP3 selects on a mask in scalar registers -- a shadow ray's lanes keep theirs)
+            if (ok) {
+                tr.t_max = t;
+                const auto m = lr_ballot(shadow);
+                const auto keep = [](auto &dst, auto v, unsigned long long mask) { asm("v_cndmask_b32_e64 %0, %1, %0, %2" : "+v"(dst) : "v"(v), "s"(mask)); };
+                if (!shadow) { tr.hit.inst = __float_as_uint(a.w), tr.hit.prim = __float_as_uint(b.w); }// (dead in the pool kernels)
+                keep(tr.hit.u, u, m), keep(tr.hit.v, v, m);
+                keep(tr.hit.tri, ref & kLeafIndexMask, m);
+            }
+            found = ok && shadow;
+            if (found) { tr.occluded = true; }
+            return found;
+        }
         if (ok) {
             tr.t_max = t;
             if (!shadow) {
