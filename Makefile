@@ -124,6 +124,10 @@ lrhip_bsdf_FLAGS = $(CALL_SAFE_FLAGS) -ffp-contract=off -fhip-fp32-correctly-rou
 # lrhip_light.o holds the kernels of the light queries (csrc/hip/light_kernel.h): the texture lookup and the environment's evaluate / sample are
 # real calls, and a query hands ONE light sample to its caller, so it is built as lrhip_bsdf.o is, for the reason given there
 lrhip_light_FLAGS = $(lrhip_bsdf_FLAGS)
+# lrhip_camera.o holds the kernels of the camera, sampler and film queries (csrc/hip/camera_kernel.h).  They make no real call, so they need no safe
+# flag; they are built with the oracle's arithmetic because a query hands ONE number, ray or weight to its caller: the Sobol sampler's pixel draw has
+# a multiply-subtract that contraction would fuse, the camera's normalize a division and the filter's weight another
+lrhip_camera_FLAGS = -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-approx-func
 $(HIP_OBJ): $(OBJDIR)/%.o: $(HIPDIR)/%.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $($*_FLAGS) -c -o $@ $<

@@ -23,6 +23,10 @@
  *   lrhip_query_bsdf               (no reference entry point: Surface::Closure::evaluate / sample at the caller's hits)
  *   lrhip_query_light              (no reference entry point: LightSampler::Instance::sample / evaluate_hit / evaluate_miss at the caller's hits,
  *                                  DESIGN §4.15)
+ *   lrhip_query_sampler            (no reference entry point: Sampler::Instance::start / generate_1d / generate_2d / generate_pixel_2d with the
+ *                                  state in the caller's hands)
+ *   lrhip_query_camera             (no reference entry point: Camera::Instance::generate_ray for the caller's pixels and numbers)
+ *   lrhip_film_splat               (no reference entry point: ColorFilmInstance::_accumulate for the caller's values)
  *   lrhip_set_instance_transforms  (Geometry::update for matrices the caller holds, computed on the device)
  *   lrhip_set_mesh_vertices        (no reference equivalent: new vertex positions for one mesh, re-baked and refitted on the device)
  *   lrhip_get_counters             (no reference equivalent; roofline accounting)
@@ -453,6 +457,119 @@ typedef struct lrhip_light_query_params {
 int lrhip_query_light(lrhip_ctx *ctx, const lrhip_light_query_params *params);
 /* HIP-event time of the kernel(s) of the last lrhip_query_light call (a host-pointer call: summed over its chunks), in ms; synchronises */
 double lrhip_last_light_ms(lrhip_ctx *ctx);
+
+/* Camera, sampler and film queries: the three ends of a render -- where its random numbers come from, where its paths start
+ * and where its samples go -- as queries in the style of the ones above, so that a whole lrhip_render can be written as a loop over queries on
+ * the device: start the streams, draw, make camera rays, trace / shade with lrhip_trace_rays, lrhip_query_surface, lrhip_query_bsdf and
+ * lrhip_query_light, draw again per vertex, and splat weight x Li into the film that lrhip_film_download, lrhip_film_reduce and the denoiser read.
+ * The kernels make the renderers' own calls (PathSampler<>::start / next_*, camera_ray, film_accumulate) and are built with the oracle's
+ * arithmetic (no contraction, correctly rounded division and square root): numbers, rays and weights are those of the reference, bit for bit.
+ *
+ * lrhip_query_sampler: Sampler::Instance with its state made explicit, so that a caller draws a path's numbers bounce by bounce.
+ *   state           uint32_t[4] per record, read (unless LRHIP_SAMPLER_START) and written: the stream's position.  Opaque, and valid only for
+ *                   the scene upload that made it (it names the scene's sampler kind, seed, tables).  The Independent sampler uses word 0 and
+ *                   writes the other words 0.  A state the caller damaged never faults: what would index a table is brought into its range.
+ *   LRHIP_SAMPLER_START  before drawing, the state is initialised as Li initialises it for stream id j at sample index s:
+ *                   j = streams ? streams[k] : k, the stream of pixel (j mod W, (j div W) mod H), as for lrhip_trace_radiance; the TileShared
+ *                   wrapper and its jitter are applied by the start itself.  s = indices ? indices[k] : sample_index.  Without the flag,
+ *                   streams and indices are not read.
+ *   pattern         host memory always: pattern_count <= LRHIP_SAMPLER_MAX_DRAWS codes, drawn in order for every record.  The three kinds are
+ *                   NOT interchangeable: LRHIP_DRAW_2D is generate_2d -- PaddedSobol shares one permutation between its two dimensions, so
+ *                   it is not two 1-D draws, and Sobol wraps its dimension counter one early for a pair -- and LRHIP_DRAW_PIXEL_2D is
+ *                   generate_pixel_2d: for Sobol dimensions 0 / 1 against the pixel, for the others a 2-D draw.  An empty pattern with
+ *                   LRHIP_SAMPLER_START only makes states; without the flag it does nothing.
+ *   out             float[count][D], row-major, D = the pattern's number of floats (1 per 1-D draw, 2 per other; at most 128).  May be NULL
+ *                   when D = 0.
+ *   Draw order of MegaPath's Li (megapath_kernel.h): per sample LRHIP_DRAW_PIXEL_2D; then LRHIP_DRAW_2D for the lens iff the camera is a thin
+ *                   lens.  Then per vertex that is shaded: 1-D light selection and 2-D light surface (both only where the scene has lights or an
+ *                   environment), 1-D lobe, 2-D BSDF, and from depth + 1 >= rr_depth on a 1-D Russian-roulette number.  A vertex that is a miss
+ *                   or carries no surface draws nothing.
+ *   PaddedSobol     the permutation's length is the scene's sampler.spp, so sample indices at or beyond it repeat earlier streams: index s takes
+ *                   the permutation slot of s mod spp (under the scramble of its own hash) and adds no new stratum.  A length that is no power
+ *                   of two: the index itself is taken modulo it, where the reference's cycle walk need not end.
+ *   Kernels         an Independent scene runs the PathSampler<false> instantiation, every other the run-time generic one -- the renderers' split.
+ *
+ * lrhip_query_camera: Camera::Instance::generate_ray with the filter's importance sampling, a pure function -- no sampler is touched.
+ *   pixels          uint32_t[count] pixel ids py * W + px, or NULL: record k is pixel k (then count <= W * H).
+ *   u               float[4][count] = (u_filter.x, u_filter.y, u_lens.x, u_lens.y): what LRHIP_DRAW_PIXEL_2D and, for a thin lens, the following
+ *                   LRHIP_DRAW_2D gave.  u_lens is not looked at by the other cameras.
+ *   out_rays        lrhip_ray[count], exactly the ray the renderers start: origin and unit direction in world space through the uploaded
+ *                   camera_to_world, at the time the scene was moved to; t_min, t_max = the clip planes over the cosine to the axis.  An array of
+ *                   its own, so that it goes into lrhip_trace_rays as it stands.
+ *   out             lrhip_camera_sample[count].  weight: the filter's f / pdf -- exactly 1 for Box, negative in the lobes of Mitchell / Lanczos;
+ *                   a path's throughput starts as it.  film_x, film_y: the continuous film position pixel + 0.5 + offset.  pixel: the id.
+ *   THE INVALID RECORD  a pixel id >= W * H or a non-finite u that is looked at: a zero ray (the ray queries screen it), weight 0, film position
+ *                   0 and pixel = LR_INVALID_ID.
+ *
+ * lrhip_film_splat: samples into the film.
+ *   pixels          as above (NULL: record k goes to pixel k, count <= W * H).  A pixel id >= W * H is skipped.
+ *   values          float[4][count] = (r, g, b, ignored): the caller has already multiplied the camera weight and the shutter weight in.
+ *   clamp           0 = the scene's film clamp.
+ *   Rule            ColorFilmInstance::_accumulate (src/films/color.cpp:107-130, effective spp 1): a record with a NaN or infinite component is
+ *                   rejected and n is not incremented; otherwise the value is scaled down so that its largest component's magnitude is at most
+ *                   the clamp, and (r, g, b, 1) is added to the pixel's float4 of the film the context accumulates into -- its own, or
+ *                   lrhip_bind_film's.
+ *   Ordering        on the context's stream: behind earlier renders, before later ones and downloads.
+ *   Determinism     when the pixels of one call are distinct (pixels == NULL always is) each pixel receives one add and the film is
+ *                   bit-determined.  Several records of one pixel in one call are added by float atomics in no fixed order: the result is the
+ *                   same up to the order of float additions (n, a small integer, is exact).
+ *   Scope           every scene whose context holds a film -- in this library every context does, an AOV scene's included (its auxiliary buffers
+ *                   are not written).  LRHIP_ERROR_UNSUPPORTED if the context holds none.
+ *
+ *   Pointers        as for lrhip_query_light.  With LRHIP_RAY_DEVICE_POINTERS every array but pattern is device memory -- state, u, values,
+ *                   out_rays, out 16-byte aligned, streams, indices, pixels 4-byte aligned, else LRHIP_ERROR_INVALID -- and the call is
+ *                   asynchronous on the context's stream.  Without it they are host memory, staged 2^20 records at a time through context-owned
+ *                   buffers released with the context, and the call synchronises.
+ *   Errors          LRHIP_ERROR_INVALID before any upload, with count > 0 for a NULL required array, for unknown flags, an unknown draw code,
+ *                   more than LRHIP_SAMPLER_MAX_DRAWS draws, a negative or NaN clamp, misaligned device pointers, count > LRHIP_RAY_MAX_COUNT,
+ *                   and count > W * H without pixels.  count == 0 launches nothing.
+ *   Determinism     a record's result is a function of (record, scene) only: bit-identical from run to run and wherever the record stands in
+ *                   the batch.  Film (but for the splat), AOV buffers, counters and lrhip_last_variant are untouched.
+ *   Not done        the closure's eta for Russian roulette (lrhip_query_bsdf does not report it); filtered splatting across pixels (the
+ *                   reference's film takes one pixel per sample); AOV buffers; a fixed order for several splats of one pixel in one call; a
+ *                   fused start-to-splat kernel.                                                                                          */
+#define LRHIP_DRAW_1D 0u
+#define LRHIP_DRAW_2D 1u
+#define LRHIP_DRAW_PIXEL_2D 2u
+#define LRHIP_SAMPLER_MAX_DRAWS 64u
+#define LRHIP_SAMPLER_START 128u
+typedef struct lrhip_sampler_query_params {
+    void *state;              /* uint32_t[4][count] */
+    const uint32_t *streams;  /* LRHIP_SAMPLER_START: uint32_t[count] or NULL (stream k) */
+    const uint32_t *indices;  /* LRHIP_SAMPLER_START: uint32_t[count] or NULL (sample_index) */
+    const uint32_t *pattern;  /* HOST memory: LRHIP_DRAW_*[pattern_count] */
+    float *out;               /* float[count][D]; may be NULL when D = 0 */
+    uint64_t count;           /* 0 is legal and launches nothing; at most LRHIP_RAY_MAX_COUNT */
+    uint32_t pattern_count;   /* at most LRHIP_SAMPLER_MAX_DRAWS */
+    uint32_t sample_index;
+    uint32_t flags;           /* LRHIP_RAY_DEVICE_POINTERS, LRHIP_SAMPLER_START */
+    uint32_t reserved;        /* 0 */
+} lrhip_sampler_query_params;
+int lrhip_query_sampler(lrhip_ctx *ctx, const lrhip_sampler_query_params *params);
+typedef struct lrhip_camera_sample {          /* 16 bytes, one dwordx4 store */
+    float weight;       float film_x, film_y; /* filter f / pdf; continuous film position */
+    uint32_t pixel;                           /* py * W + px; LR_INVALID_ID in the invalid record */
+} lrhip_camera_sample;
+typedef struct lrhip_camera_query_params {
+    const uint32_t *pixels;   /* uint32_t[count] or NULL (pixel k) */
+    const void *u;            /* float[4][count] = (u_filter.x, u_filter.y, u_lens.x, u_lens.y) */
+    void *out_rays;           /* lrhip_ray[count] */
+    void *out;                /* lrhip_camera_sample[count] */
+    uint64_t count;
+    uint32_t flags;           /* LRHIP_RAY_DEVICE_POINTERS */
+    uint32_t reserved;        /* 0 */
+} lrhip_camera_query_params;
+int lrhip_query_camera(lrhip_ctx *ctx, const lrhip_camera_query_params *params);
+typedef struct lrhip_film_splat_params {
+    const uint32_t *pixels;   /* uint32_t[count] or NULL (pixel k) */
+    const void *values;       /* float[4][count] = (r, g, b, -) */
+    uint64_t count;
+    uint32_t flags;           /* LRHIP_RAY_DEVICE_POINTERS */
+    float clamp;              /* 0 = the scene's film clamp */
+} lrhip_film_splat_params;
+int lrhip_film_splat(lrhip_ctx *ctx, const lrhip_film_splat_params *params);
+/* HIP-event time of the kernel(s) of the last of these three calls (a host-pointer call: summed over its chunks), in ms; synchronises */
+double lrhip_last_camera_ms(lrhip_ctx *ctx);
 
 /* Moving instances on the device: Geometry::update (src/base/geometry.cpp:194-216) for object-to-world matrices the caller holds --
  * an animation frame, a physics step whose matrices are a tensor on the GPU, a drag in an editor -- between two renders or queries, without a

@@ -191,6 +191,28 @@ class LightQueryParams(C.Structure):
                 ("mode", u32), ("flags", u32)]
 
 
+class SamplerQueryParams(C.Structure):
+    """lrhip_sampler_query_params (include/lrhip.h)"""
+    _fields_ = [("state", C.c_void_p), ("streams", C.c_void_p), ("indices", C.c_void_p), ("pattern", C.c_void_p), ("out", C.c_void_p),
+                ("count", u64), ("pattern_count", u32), ("sample_index", u32), ("flags", u32), ("reserved", u32)]
+
+
+class CameraSample(C.Structure):
+    """lrhip_camera_sample (include/lrhip.h): one row of the [N, 4] 32-bit buffer behind CameraRays"""
+    _fields_ = [("weight", f32), ("film_x", f32), ("film_y", f32), ("pixel", u32)]
+
+
+class CameraQueryParams(C.Structure):
+    """lrhip_camera_query_params (include/lrhip.h)"""
+    _fields_ = [("pixels", C.c_void_p), ("u", C.c_void_p), ("out_rays", C.c_void_p), ("out", C.c_void_p), ("count", u64), ("flags", u32),
+                ("reserved", u32)]
+
+
+class FilmSplatParams(C.Structure):
+    """lrhip_film_splat_params (include/lrhip.h)"""
+    _fields_ = [("pixels", C.c_void_p), ("values", C.c_void_p), ("count", u64), ("flags", u32), ("clamp", f32)]
+
+
 class InstanceUpdateParams(C.Structure):
     """lrhip_instance_update_params (include/lrhip.h)"""
     _fields_ = [("object_to_world", C.c_void_p), ("instances", C.c_void_p), ("count", u64), ("flags", u32)]
@@ -220,10 +242,16 @@ LIGHT_SAMPLE, LIGHT_EVALUATE = 0, 1  # lrhip_light_query_params::mode: LRHIP_LIG
 LIGHT_FROM_POINTS = 64  # LRHIP_LIGHT_FROM_POINTS
 # lrhip_light_result::kind: LRHIP_LIGHT_KIND_AREA / ENVIRONMENT / NONE (LR_INVALID_ID in the invalid record)
 LIGHT_KIND_AREA, LIGHT_KIND_ENVIRONMENT, LIGHT_KIND_NONE = 0, 1, 2
+# lrhip_sampler_query_params::pattern: LRHIP_DRAW_1D / LRHIP_DRAW_2D / LRHIP_DRAW_PIXEL_2D; LRHIP_SAMPLER_MAX_DRAWS; LRHIP_SAMPLER_START
+DRAW_1D, DRAW_2D, DRAW_PIXEL_2D = 0, 1, 2
+SAMPLER_MAX_DRAWS = 64
+SAMPLER_START = 128
 
 STRUCTS = {"lrhip_surface_point": SurfacePoint, "lrhip_surface_query_params": SurfaceQueryParams,
 "lrhip_bsdf_result": BsdfResult, "lrhip_bsdf_query_params": BsdfQueryParams,
 "lrhip_light_result": LightResult, "lrhip_light_query_params": LightQueryParams,
+"lrhip_sampler_query_params": SamplerQueryParams, "lrhip_camera_sample": CameraSample, "lrhip_camera_query_params": CameraQueryParams,
+"lrhip_film_splat_params": FilmSplatParams,
 "lrhip_denoise_params": DenoiseParams, "lrhip_ray": Ray, "lrhip_ray_hit": RayHit, "lrhip_ray_query_params": RayQueryParams,
            "lrhip_radiance_query_params": RadianceQueryParams, "lrhip_instance_update_params": InstanceUpdateParams,
            "lrhip_mesh_update_params": MeshUpdateParams,
@@ -353,6 +381,11 @@ def hip_lib(path: str | None = None) -> C.CDLL:
         lib.lrhip_query_light.argtypes = [C.c_void_p, C.POINTER(LightQueryParams)]
         lib.lrhip_last_light_ms.restype = C.c_double
         lib.lrhip_last_light_ms.argtypes = [C.c_void_p]
+        lib.lrhip_query_sampler.argtypes = [C.c_void_p, C.POINTER(SamplerQueryParams)]
+        lib.lrhip_query_camera.argtypes = [C.c_void_p, C.POINTER(CameraQueryParams)]
+        lib.lrhip_film_splat.argtypes = [C.c_void_p, C.POINTER(FilmSplatParams)]
+        lib.lrhip_last_camera_ms.restype = C.c_double
+        lib.lrhip_last_camera_ms.argtypes = [C.c_void_p]
         lib.lrhip_set_instance_transforms.argtypes = [C.c_void_p, C.POINTER(InstanceUpdateParams)]
         lib.lrhip_last_instance_update_ms.restype = C.c_double
         lib.lrhip_last_instance_update_ms.argtypes = [C.c_void_p]

@@ -141,6 +141,9 @@ void lrhip_destroy(lrhip_ctx *ctx) {
     ctx->light_rays.release(), ctx->light_out.release();
     if (ctx->light_begin) { (void)hipEventDestroy(ctx->light_begin); }
     if (ctx->light_end) { (void)hipEventDestroy(ctx->light_end); }
+    ctx->camera_state.release(), ctx->camera_streams.release(), ctx->camera_indices.release(), ctx->camera_out.release();
+    if (ctx->camera_begin) { (void)hipEventDestroy(ctx->camera_begin); }
+    if (ctx->camera_end) { (void)hipEventDestroy(ctx->camera_end); }
     ctx->spill.release(), ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->wf_counts.release(), ctx->wf_accum.release();
     ctx->pool.release(), ctx->counters.release(), ctx->work_counter.release(), ctx->scene_record.release();
     if (ctx->ev_begin) { (void)hipEventDestroy(ctx->ev_begin); }

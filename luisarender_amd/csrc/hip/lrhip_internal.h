@@ -13,6 +13,7 @@
 //   lrhip_surface.hip    surface queries: position, normals, uv, material and emission at caller-supplied hits (surface_kernel.h)
 //   lrhip_bsdf.hip       BSDF queries: the closure evaluated or sampled at caller-supplied hits (bsdf_kernel.h)
 //   lrhip_light.hip      light queries: the emitters sampled from, or evaluated at, caller-supplied hits (light_kernel.h)
+//   lrhip_camera.hip     camera, sampler and film queries: sampler streams, camera rays, splats into the film (camera_kernel.h)
 //   lrhip_instance_update.hip  moving instances on the device: re-bake, refit and re-quantise (instance_update_kernels.h); the table test hook
 //   lrhip_mesh_update.hip      deforming a mesh on the device: vertex write, normal recompute, marking (mesh_update_kernels.h), then the re-bake and refit
 // Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
@@ -232,6 +233,14 @@ struct lrhip_ctx {
     hipEvent_t light_begin{nullptr}, light_end{nullptr};
     double light_ms{0.};
     bool light_pending{false};
+    // camera, sampler and film queries (lrhip_camera.hip).  Of the context: the staging buffers of a host-pointer call -- sampler states (the camera
+    // query's 16-byte records go through the same buffer), stream or pixel ids, sample indices, the drawn numbers; the caller's numbers and values go
+    // through bsdf_dirs, the camera rays through light_rays -- they grow on demand and outlive the scene --, the events around the last launch, the
+    // kernel time of the last call's finished launches and whether one is still to be read (lrhip_last_camera_ms)
+    lrh::DeviceBuffer camera_state, camera_streams, camera_indices, camera_out;
+    hipEvent_t camera_begin{nullptr}, camera_end{nullptr};
+    double camera_ms{0.};
+    bool camera_pending{false};
 };
 
 namespace lrh {

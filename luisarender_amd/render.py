@@ -233,6 +233,112 @@ def check_light_args(hits=None, u=None, points=None, rays=None, device: int | No
     return kind
 
 
+def parse_sampler_pattern(pattern: str) -> tuple[list[int], int]:
+    """A draw pattern for MegaPathRenderer.sampler_draw: a string over "1" (LRHIP_DRAW_1D), "2" (LRHIP_DRAW_2D) and "p" (LRHIP_DRAW_PIXEL_2D),
+    at most 64 draws.  Returns (the codes, the number of floats per record: 1 per "1", 2 per other, at most 128).  ValueError for anything else."""
+    if not isinstance(pattern, str):
+        raise ValueError(f"sampler: the pattern must be a string over '1', '2', 'p', not {type(pattern).__name__}")
+    codes = []
+    for c in pattern:
+        if c not in "12p":
+            raise ValueError(f"sampler: unknown draw {c!r} in the pattern (known: '1', '2', 'p')")
+        codes.append({"1": _ffi.DRAW_1D, "2": _ffi.DRAW_2D, "p": _ffi.DRAW_PIXEL_2D}[c])
+    if len(codes) > _ffi.SAMPLER_MAX_DRAWS:
+        raise ValueError(f"sampler: {len(codes)} draws in one pattern, at most {_ffi.SAMPLER_MAX_DRAWS}")
+    floats = sum(1 if c == _ffi.DRAW_1D else 2 for c in codes)
+    if floats > 2 * _ffi.SAMPLER_MAX_DRAWS:  # (cannot happen with 64 draws of at most 2 floats: kept as the stated bound of `out`)
+        raise ValueError(f"sampler: {floats} floats per record, at most {2 * _ffi.SAMPLER_MAX_DRAWS}")
+    return codes, floats
+
+
+def _query_array(prefix: str, name: str, a, shapes, dtype_name: str, device: int | None, like=None) -> str:
+    # `a` is a contiguous numpy array, or torch tensor on GPU `device`, of one of `shapes` (None = any N) and of dtype `dtype_name` (a uint32
+    # array is int32 in torch); of `like`'s kind, device and N where `like` is given.  Returns its kind
+    if isinstance(a, np.ndarray):
+        kind, contiguous = "numpy", a.flags["C_CONTIGUOUS"]
+    elif type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr"):
+        kind, contiguous = "torch", a.is_contiguous()
+        if a.device.type != "cuda":
+            raise ValueError(f"{prefix}: the {name} tensor is on {a.device}, not on a GPU")
+        if device is not None and a.device.index != device:
+            raise ValueError(f"{prefix}: the {name} tensor is on {a.device}, the renderer on GPU {device}")
+    else:
+        raise TypeError(f"{prefix}: {name} must be a numpy array or a torch tensor, not {type(a).__name__}")
+    want = "int32" if (kind == "torch" and dtype_name == "uint32") else dtype_name
+    if str(a.dtype).split(".")[-1] != want:
+        raise ValueError(f"{prefix}: {name} must be {want}, not {a.dtype}")
+    if not any(a.ndim == len(s) and all(w is None or int(d) == w for d, w in zip(a.shape, s)) for s in shapes):
+        raise ValueError(f"{prefix}: {name} must have shape {' or '.join(str(['N' if w is None else w for w in s]) for s in shapes)}, "
+                         f"not {tuple(a.shape)}")
+    if not contiguous:
+        raise ValueError(f"{prefix}: {name} is read in place and must be contiguous")
+    if like is not None:
+        like_kind = "numpy" if isinstance(like, np.ndarray) else "torch"
+        if kind != like_kind:
+            raise ValueError(f"{prefix}: {name} is a {kind} array, the other arrays are {like_kind} arrays")
+        if kind == "torch" and a.device != like.device:
+            raise ValueError(f"{prefix}: {name} is on {a.device}, the other arrays on {like.device}")
+        if int(a.shape[0]) != int(like.shape[0]):
+            raise ValueError(f"{prefix}: {int(a.shape[0])} rows of {name} for {int(like.shape[0])} records")
+    return kind
+
+
+def check_sampler_args(state=None, pattern: str = "", streams=None, indices=None, count: int | None = None, sample: int = 0,
+                       device: int | None = None) -> str:
+    """What MegaPathRenderer.sampler_start (state None) / sampler_draw (state given) accept (no device needed).
+    start: streams and indices None or uint32 [N] (torch: int32, read as uint32); count None or the number of records -- required when neither
+    array is given, and equal to N otherwise; sample an integer in [0, 2^32).
+    draw: state uint32 [N, 4] (torch: int32), as sampler_start returned it; streams, indices and count must be None.
+    pattern: what parse_sampler_pattern accepts.  All arrays are of one kind (numpy, or torch on one GPU), contiguous, with the same N.  Returns
+    "numpy" or "torch" ("numpy" for a start without arrays); TypeError for an argument that is no array or tensor at all, ValueError otherwise."""
+    parse_sampler_pattern(pattern)
+    if state is not None:
+        if streams is not None or indices is not None or count is not None:
+            raise ValueError("sampler: sampler_draw takes a state and a pattern; streams, indices and count belong to sampler_start")
+        return _query_array("sampler", "state", state, [(None, 4)], "uint32", device)
+    if isinstance(sample, bool) or not isinstance(sample, (int, np.integer)) or not 0 <= sample <= 0xFFFFFFFF:
+        raise ValueError(f"sampler: sample must be a 32-bit sample index, not {sample!r}")
+    if count is not None and (isinstance(count, bool) or not isinstance(count, (int, np.integer)) or not 0 <= count <= 0x7FFFFFFF):
+        raise ValueError(f"sampler: count must be an integer in [0, 2^31), not {count!r}")
+    kind, first = "numpy", None
+    for name, a in (("streams", streams), ("indices", indices)):
+        if a is not None:
+            kind = _query_array("sampler", name, a, [(None,)], "uint32", device, first)
+            first = a if first is None else first
+    if first is None and count is None:
+        raise ValueError("sampler: sampler_start needs streams, indices or count")
+    if first is not None and count is not None and int(first.shape[0]) != count:
+        raise ValueError(f"sampler: count is {count}, the arrays have {int(first.shape[0])} rows")
+    return kind
+
+
+def check_camera_args(u, pixels=None, pixel_count: int | None = None, device: int | None = None) -> str:
+    """What MegaPathRenderer.camera_rays accepts (no device needed).  u: float32 [N, 4] = (u_filter.x, u_filter.y, u_lens.x, u_lens.y), read in
+    place, or [N, 2] = u_filter alone, padded by a copy (for a camera that is no thin lens).  pixels: None (record k is pixel k; then
+    N <= pixel_count where that is given) or uint32 [N] pixel ids py * W + px (torch: int32, read as uint32).  Both of one kind (numpy, or torch
+    on one GPU) and contiguous.  Returns "numpy" or "torch"; TypeError for an argument that is no array or tensor, ValueError otherwise."""
+    kind = _query_array("camera", "u", u, [(None, 4), (None, 2)], "float32", device)
+    if pixels is not None:
+        _query_array("camera", "pixels", pixels, [(None,)], "uint32", device, u)
+    elif pixel_count is not None and int(u.shape[0]) > pixel_count:
+        raise ValueError(f"camera: {int(u.shape[0])} records without pixels, the frame has {pixel_count} pixels")
+    return kind
+
+
+def check_splat_args(values, pixels=None, clamp=None, pixel_count: int | None = None, device: int | None = None) -> str:
+    """What MegaPathRenderer.film_splat accepts (no device needed).  values: float32 [N, 4] = (r, g, b, ignored), read in place, or [N, 3],
+    padded by a copy.  pixels: as for check_camera_args.  clamp: None (the scene's film clamp) or a positive finite number.  Returns "numpy" or
+    "torch"; TypeError for an argument that is no array or tensor, ValueError otherwise."""
+    kind = _query_array("splat", "values", values, [(None, 4), (None, 3)], "float32", device)
+    if pixels is not None:
+        _query_array("splat", "pixels", pixels, [(None,)], "uint32", device, values)
+    elif pixel_count is not None and int(values.shape[0]) > pixel_count:
+        raise ValueError(f"splat: {int(values.shape[0])} records without pixels, the frame has {pixel_count} pixels")
+    if clamp is not None and not (0.0 < float(clamp) < float("inf")):
+        raise ValueError(f"splat: clamp must be a positive finite number or None (the scene's film clamp), not {clamp}")
+    return kind
+
+
 def check_instance_transforms(matrices, instances=None, instance_count: int | None = None, device: int | None = None) -> str:
     """What MegaPathRenderer.set_instance_transforms and Scene.set_instance_transforms accept (no device needed).  matrices: float32,
     contiguous, [N, 4, 4] or [N, 16] in COLUMN-MAJOR storage -- matrices[i, c, r] (flat: [i, 4 c + r]) is row r of column c, the layout of
@@ -462,6 +568,29 @@ class LightSamples(LightResults):
     def __init__(self, rays, buffer):
         super().__init__(buffer)
         self.rays = rays
+
+
+class CameraRays:
+    """Results of MegaPathRenderer.camera_rays: `rays`, the [N, 8] float32 buffer of camera rays (ox, oy, oz, t_min, dx, dy, dz, t_max) that
+    trace(rays) takes as it stands, and views (no copies) of ONE [N, 4] 32-bit buffer of lrhip_camera_sample records -- `buffer`, a float32
+    numpy array or, for the torch path, the float32 tensor on the device.  weight: [N], the filter's f / pdf; film_xy: [N, 2], the continuous
+    film position; pixel: uint32 (torch: int32, LR_INVALID_ID reads -1); valid: bool, false for the invalid record."""
+
+    def __init__(self, rays, buffer):
+        self.rays, self.buffer = rays, buffer
+        if isinstance(buffer, np.ndarray):
+            ids = buffer.view(np.uint32)
+        else:
+            import torch
+            ids = buffer.view(torch.int32)
+        self.weight, self.film_xy, self.pixel = buffer[:, 0], buffer[:, 1:3], ids[:, 3]
+
+    @property
+    def valid(self):
+        return self.pixel != (0xFFFFFFFF if isinstance(self.buffer, np.ndarray) else -1)
+
+    def __len__(self) -> int:
+        return int(self.buffer.shape[0])
 
 
 class MegaPathRenderer:
@@ -817,6 +946,149 @@ class MegaPathRenderer:
     def last_light_ms(self) -> float:
         """lrhip_last_light_ms: HIP-event time of the kernel(s) of the last light_sample() / light_evaluate()"""
         return float(self._lib.lrhip_last_light_ms(self._ctx))
+
+    def _sampler(self, kind: str, state, pattern: str, streams, indices, sample: int, start: bool, sync: bool):
+        # one lrhip_query_sampler call over `state` ([N, 4], written in place); returns the drawn numbers [N, D]
+        codes, floats = parse_sampler_pattern(pattern)
+        n = int(state.shape[0])
+        p = _ffi.SamplerQueryParams()
+        p.count, p.pattern_count, p.sample_index = n, len(codes), sample
+        p.flags = _ffi.SAMPLER_START if start else 0
+        table = (C.c_uint32 * max(len(codes), 1))(*codes)
+        p.pattern = C.cast(table, C.c_void_p)
+        if kind == "numpy":
+            out = np.empty((n, floats), np.float32)
+            p.state, p.out = state.ctypes.data, out.ctypes.data if floats else None
+            p.streams = streams.ctypes.data if streams is not None else None
+            p.indices = indices.ctypes.data if indices is not None else None
+            self._check(self._lib.lrhip_query_sampler(self._ctx, C.byref(p)))
+            return out
+        import torch
+        out = torch.empty((n, floats), dtype=torch.float32, device=state.device)
+        if n != 0 and (state.data_ptr() % 16 != 0 or (floats and out.data_ptr() % 16 != 0)):
+            raise ValueError("sampler: the state must be 16-byte aligned on the device")
+        p.state, p.out = state.data_ptr(), out.data_ptr() if floats else None
+        p.streams = streams.data_ptr() if streams is not None else None
+        p.indices = indices.data_ptr() if indices is not None else None
+        p.flags |= _ffi.RAY_DEVICE_POINTERS
+        if sync:
+            torch.cuda.current_stream(state.device).synchronize()
+        self._check(self._lib.lrhip_query_sampler(self._ctx, C.byref(p)))
+        if sync:
+            self.synchronize()
+        return out
+
+    def sampler_start(self, streams=None, sample: int = 0, count: int | None = None, indices=None, on_device: bool = False, sync: bool = True):
+        """lrhip_query_sampler with LRHIP_SAMPLER_START and an empty pattern (lrhip.h has the semantics): the states of the scene's sampler
+        streams as Li starts them -- stream streams[k] (None: k; stream py * W + px is pixel (px, py)'s, as in radiance()) at sample index
+        indices[k] (None: `sample`).  streams, indices, count: what check_sampler_args accepts.  Returns the [N, 4] state, uint32 numpy or,
+        for tensors on this renderer's GPU (or on_device=True where no array says so), int32 torch on the device.  The state is opaque and
+        valid for this upload only; sampler_draw advances it."""
+        kind = check_sampler_args(None, "", streams, indices, count, sample, self._device)
+        first = streams if streams is not None else indices
+        n = int(first.shape[0]) if first is not None else int(count)
+        if kind == "numpy" and not (on_device and first is None):
+            state = np.empty((n, 4), np.uint32)
+        else:
+            import torch
+            kind = "torch"
+            state = torch.empty((n, 4), dtype=torch.int32, device=first.device if first is not None else torch.device("cuda", self._device))
+        self._sampler(kind, state, "", streams, indices, int(sample), True, sync)
+        return state
+
+    def sampler_draw(self, state, pattern: str, sync: bool = True):
+        """lrhip_query_sampler: draws `pattern` -- a string over "1" (1-D), "2" (2-D) and "p" (pixel 2-D), at most 64 draws; the three are NOT
+        interchangeable (lrhip.h) -- from every stream of `state`, which is advanced IN PLACE.  Returns the numbers, float32 [N, D], of the
+        state's kind (numpy, or torch on the device; synchronisation as in trace()).  MegaPath's Li draws "p", "2" iff the camera is a thin
+        lens, then per shaded vertex "1212" (light selection, light surface, lobe, BSDF) and from rr_depth on one more "1"."""
+        kind = check_sampler_args(state, pattern, device=self._device)
+        return self._sampler(kind, state, pattern, None, None, 0, False, sync)
+
+    def camera_rays(self, u, pixels=None, sync: bool = True) -> CameraRays:
+        """lrhip_query_camera (lrhip.h has the semantics): the scene's camera ray for each pixel id (None: record k is pixel k) and the numbers
+        u = (u_filter.x, u_filter.y, u_lens.x, u_lens.y) -- what sampler_draw gave for "p2" (a camera that is no thin lens: "p" alone, [N, 2]).
+        u, pixels: what check_camera_args accepts.  Returns CameraRays: the rays, ready for trace(), the filter weight a path's throughput
+        starts as, the film position and the pixel.  numpy arrays go through host pointers; torch tensors on this renderer's GPU are read in
+        place and the results stay on the device (synchronisation as in trace())."""
+        kind = check_camera_args(u, pixels, self.width * self.height, self._device)
+        n = int(u.shape[0])
+        padded = u.shape[1] == 2
+        if padded and self._scene is not None and int(self._scene.view().camera.kind) == 1:  # LR_CAMERA_THIN_LENS
+            raise ValueError("camera: a thin lens needs u = (u_filter, u_lens), [N, 4]")
+        p = _ffi.CameraQueryParams()
+        p.count = n
+        if kind == "numpy":
+            if padded:
+                u = np.concatenate([u, np.full((n, 2), 0.5, np.float32)], axis=1)
+            rays, out = np.empty((n, 8), np.float32), np.empty((n, 4), np.float32)
+            p.u, p.out_rays, p.out = u.ctypes.data, rays.ctypes.data, out.ctypes.data
+            p.pixels = pixels.ctypes.data if pixels is not None else None
+            self._check(self._lib.lrhip_query_camera(self._ctx, C.byref(p)))
+            return CameraRays(rays, out)
+        import torch
+        if padded:
+            u = torch.nn.functional.pad(u, (0, 2), value=0.5).contiguous()
+        if sync or padded:  # (the padding copy runs on torch's stream, the query on the context's: the copy is waited for whatever `sync` says)
+            torch.cuda.current_stream(u.device).synchronize()
+        rays = torch.empty((n, 8), dtype=torch.float32, device=u.device)
+        out = torch.empty((n, 4), dtype=torch.float32, device=u.device)
+        if n != 0 and u.data_ptr() % 16 != 0:
+            raise ValueError("camera: u must be 16-byte aligned on the device")
+        p.u, p.out_rays, p.out = u.data_ptr(), rays.data_ptr(), out.data_ptr()
+        p.pixels = pixels.data_ptr() if pixels is not None else None
+        p.flags = _ffi.RAY_DEVICE_POINTERS
+        self._check(self._lib.lrhip_query_camera(self._ctx, C.byref(p)))
+        if sync or padded:  # (the padded copy must outlive the kernel that reads it)
+            self.synchronize()
+        return CameraRays(rays, out)
+
+    def camera_samples(self, sample: int, pixels=None, on_device: bool = False, sync: bool = True):
+        """The camera samples of sample index `sample` as lrhip_render takes them: sampler_start for the pixels' streams (None: every pixel of
+        the frame, in order), the pixel draw and, for a thin lens, the lens draw, then camera_rays.  Returns (CameraRays, state): the state is
+        ready for the first vertex's sampler_draw(state, "1212")."""
+        if pixels is None:
+            state = self.sampler_start(None, sample, self.width * self.height, on_device=on_device, sync=sync)
+        else:
+            state = self.sampler_start(pixels, sample, sync=sync)
+        thin_lens = int(self._scene.view().camera.kind) == 1  # LR_CAMERA_THIN_LENS
+        u = self.sampler_draw(state, "p2" if thin_lens else "p", sync=sync)
+        return self.camera_rays(u, pixels, sync=sync), state
+
+    def film_splat(self, values, pixels=None, clamp: float | None = None, sync: bool = True) -> None:
+        """lrhip_film_splat (lrhip.h has the semantics): one sample per record into the film by the reference's accumulate rule -- a NaN or
+        infinite value is rejected, a value above the clamp (None: the scene's) is scaled down by its largest component, and (r, g, b, 1) is
+        added to pixel pixels[k] (None: k) of the film the context accumulates into, in stream order with render() and download().  values,
+        pixels: what check_splat_args accepts; the caller has multiplied the camera weight and the shutter weight in.  Distinct pixels in one
+        call give a bit-determined film; several records of one pixel are added in no fixed order."""
+        kind = check_splat_args(values, pixels, clamp, self.width * self.height, self._device)
+        n = int(values.shape[0])
+        padded = values.shape[1] == 3
+        p = _ffi.FilmSplatParams()
+        p.count, p.clamp = n, 0.0 if clamp is None else clamp
+        if kind == "numpy":
+            if padded:
+                values = np.concatenate([values, np.zeros((n, 1), np.float32)], axis=1)
+            p.values = values.ctypes.data
+            p.pixels = pixels.ctypes.data if pixels is not None else None
+            self._check(self._lib.lrhip_film_splat(self._ctx, C.byref(p)))
+            return
+        import torch
+        if padded:
+            values = torch.nn.functional.pad(values, (0, 1)).contiguous()
+        if sync or padded:
+            torch.cuda.current_stream(values.device).synchronize()
+        if n != 0 and values.data_ptr() % 16 != 0:
+            raise ValueError("splat: values must be 16-byte aligned on the device")
+        p.values = values.data_ptr()
+        p.pixels = pixels.data_ptr() if pixels is not None else None
+        p.flags = _ffi.RAY_DEVICE_POINTERS
+        self._check(self._lib.lrhip_film_splat(self._ctx, C.byref(p)))
+        if sync or padded:  # (the padded copy must outlive the kernel that reads it)
+            self.synchronize()
+
+    def last_camera_ms(self) -> float:
+        """lrhip_last_camera_ms: HIP-event time of the kernel(s) of the last sampler_start() / sampler_draw() / camera_rays() / film_splat()"""
+        return float(self._lib.lrhip_last_camera_ms(self._ctx))
 
     def set_instance_transforms(self, matrices, instances=None, sync: bool = True) -> None:
         """lrhip_set_instance_transforms (lrhip.h has the semantics): move instances of the uploaded scene on the device -- their records, baked
