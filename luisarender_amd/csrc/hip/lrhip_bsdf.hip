@@ -33,12 +33,6 @@ namespace lrh {
 
 namespace {
 
-// records per chunk of a host-pointer call: 32 MiB each of hits, rays and results and 16 MiB of dirs in the staging buffers, whatever the
-// count.  Hit records and rays go through the surface and ray queries' staging buffers: every host-pointer call synchronises per chunk
-constexpr uint64_t kBsdfChunk = 1ull << 20u;
-// blocks of a launch, at most: 2^20 blocks of 256 lanes cover 2^28 records in one pass; a larger batch strides
-constexpr uint32_t kBsdfMaxBlocks = 1u << 20u;
-
 template<uint32_t MODE>
 void launch(uint32_t features, uint32_t blocks, hipStream_t stream, lrd::DScenePtr scene, const lrd::BsdfArgs &args) {
     // which interpreters the scene needs (bsdf_kernel.h): anything with Layered takes the kernel that holds both
@@ -51,50 +45,6 @@ void launch(uint32_t features, uint32_t blocks, hipStream_t stream, lrd::DSceneP
     }
 }
 
-// one launch over `count` records in device memory, between the context's bsdf events
-int query_device(lrhip_ctx *ctx, const void *hits, const void *rays, const void *dirs, void *out, uint32_t count, uint32_t mode) {
-    // the lr_mesh table of the uploaded scene, shared with the surface queries: copied once per upload
-    if (!ctx->surface_meshes_ready) {
-        const auto bytes = ctx->meshes.size() * sizeof(lr_mesh);
-        if (auto r = ensure(ctx->surface_meshes, std::max<size_t>(bytes, 16u)); r != LRHIP_OK) { return r; }
-        if (bytes != 0u) { LR_HIP_CHECK(hipMemcpyAsync(ctx->surface_meshes.ptr, ctx->meshes.data(), bytes, hipMemcpyHostToDevice, ctx->stream)); }
-        ctx->surface_meshes_ready = true;
-    }
-    lrd::BsdfArgs args{};
-    args.hits = static_cast<const float4 *>(hits), args.rays = static_cast<const float4 *>(rays), args.dirs = static_cast<const float4 *>(dirs);
-    args.out = static_cast<float4 *>(out);
-    args.meshes = static_cast<const lr_mesh *>(ctx->surface_meshes.ptr);
-    args.count = count;
-    args.triangle_count = ctx->update_counts[1], args.instance_count = ctx->update_counts[2];
-    args.mesh_count = static_cast<uint32_t>(ctx->meshes.size());
-    const auto blocks = std::min(kBsdfMaxBlocks, (count + lrd::kBlockThreads - 1u) / lrd::kBlockThreads);
-    // the scene record as the host holds it now (lrhip_render writes one per launch; none exists before the first render)
-    if (auto r = ensure(ctx->scene_record, sizeof(lrd::DScene)); r != LRHIP_OK) { return r; }
-    LR_HIP_CHECK(hipMemcpyAsync(ctx->scene_record.ptr, &ctx->scene, sizeof(lrd::DScene), hipMemcpyHostToDevice, ctx->stream));
-    const auto device_scene = (lrd::DScenePtr) static_cast<const lrd::DScene *>(ctx->scene_record.ptr);
-    // the closures of the scene's surfaces themselves -- not ctx->features, which the volumetric integrator clears of them and the sibling
-    // integrators fill with all of them --, and what lrhip_set_diagnostics forces on top (the twin tests: a lean scene on the heavier kernels)
-    const auto features = ctx->closure_features | (ctx->diag_force_features & lrd::kFeatSceneMask);
-    LR_HIP_CHECK(hipEventRecord(ctx->bsdf_begin, ctx->stream));
-    if (mode == LRHIP_BSDF_EVALUATE) { launch<lrd::kBsdfEvaluate>(features, blocks, ctx->stream, device_scene, args); }
-    else { launch<lrd::kBsdfSample>(features, blocks, ctx->stream, device_scene, args); }
-    LR_HIP_CHECK(hipGetLastError());
-    LR_HIP_CHECK(hipEventRecord(ctx->bsdf_end, ctx->stream));
-    ctx->bsdf_pending = true;
-    return LRHIP_OK;
-}
-
-// the pending launch's time joins the call's sum (synchronises with it)
-int collect_time(lrhip_ctx *ctx) {
-    if (!ctx->bsdf_pending) { return LRHIP_OK; }
-    float ms = 0.f;
-    LR_HIP_CHECK(hipEventSynchronize(ctx->bsdf_end));
-    LR_HIP_CHECK(hipEventElapsedTime(&ms, ctx->bsdf_begin, ctx->bsdf_end));
-    ctx->bsdf_ms += static_cast<double>(ms);
-    ctx->bsdf_pending = false;
-    return LRHIP_OK;
-}
-
 }// namespace
 
 }// namespace lrh
@@ -104,60 +54,41 @@ using namespace lrh;
 extern "C" {
 
 int lrhip_query_bsdf(lrhip_ctx *ctx, const lrhip_bsdf_query_params *p) {
-    if (ctx == nullptr || p == nullptr) { return fail(LRHIP_ERROR_INVALID, "lrhip_query_bsdf: NULL argument"); }
-    if ((p->flags & ~LRHIP_RAY_DEVICE_POINTERS) != 0u) { return fail(LRHIP_ERROR_INVALID, "lrhip_query_bsdf: unknown flags"); }
+    if (auto r = screen("lrhip_query_bsdf", ctx, p, LRHIP_RAY_DEVICE_POINTERS, "records"); r != LRHIP_OK) { return r; }
     if (p->mode != LRHIP_BSDF_EVALUATE && p->mode != LRHIP_BSDF_SAMPLE) { return fail(LRHIP_ERROR_INVALID, "lrhip_query_bsdf: unknown mode"); }
-    if (p->count > LRHIP_RAY_MAX_COUNT) { return fail(LRHIP_ERROR_INVALID, "lrhip_query_bsdf: more than 2^31 - 1 records"); }
-    if (!ctx->scene_ready) { return fail(LRHIP_ERROR_INVALID, "lrhip_query_bsdf: no scene uploaded"); }
     const auto device_pointers = (p->flags & LRHIP_RAY_DEVICE_POINTERS) != 0u;
     if (p->count != 0u) {
         if (p->hits == nullptr || p->dirs == nullptr || p->out == nullptr) { return fail(LRHIP_ERROR_INVALID, "lrhip_query_bsdf: hits / dirs / out is NULL"); }
-        if (device_pointers && ((reinterpret_cast<uintptr_t>(p->hits) | reinterpret_cast<uintptr_t>(p->rays) | reinterpret_cast<uintptr_t>(p->dirs) |
-                                 reinterpret_cast<uintptr_t>(p->out)) & 15u) != 0u) {
+        if (device_pointers && misaligned({{p->hits, 15u}, {p->rays, 15u}, {p->dirs, 15u}, {p->out, 15u}})) {
             return fail(LRHIP_ERROR_INVALID, "lrhip_query_bsdf: device pointers must be 16-byte aligned");
         }
     }
     if ((ctx->features & lrd::kFeatNest) != 0u) {
         return fail(LRHIP_ERROR_UNSUPPORTED, "lrhip_query_bsdf: Mix / Layered surfaces nested in each other are not supported");
     }
-    LR_HIP_CHECK(hipSetDevice(ctx->device));
-    ctx->bsdf_ms = 0.0, ctx->bsdf_pending = false;
+    if (auto r = timer_start(ctx, ctx->bsdf_timer, p->count != 0u); r != LRHIP_OK) { return r; }
     if (p->count == 0u) { return LRHIP_OK; }
-    if (ctx->bsdf_begin == nullptr) { LR_HIP_CHECK(hipEventCreate(&ctx->bsdf_begin)); }
-    if (ctx->bsdf_end == nullptr) { LR_HIP_CHECK(hipEventCreate(&ctx->bsdf_end)); }
-    if (device_pointers) { return query_device(ctx, p->hits, p->rays, p->dirs, p->out, static_cast<uint32_t>(p->count), p->mode); }
-    // host pointers: chunk by chunk through the staging buffers
-    const auto chunk = std::min<uint64_t>(p->count, kBsdfChunk);
-    if (auto r = ensure(ctx->surface_hits, chunk * sizeof(lrhip_ray_hit)); r != LRHIP_OK) { return r; }
-    if (p->rays != nullptr) {
-        if (auto r = ensure(ctx->raycast_rays, chunk * sizeof(lrhip_ray)); r != LRHIP_OK) { return r; }
-    }
-    if (auto r = ensure(ctx->bsdf_dirs, chunk * sizeof(float4)); r != LRHIP_OK) { return r; }
-    if (auto r = ensure(ctx->bsdf_out, chunk * sizeof(lrhip_bsdf_result)); r != LRHIP_OK) { return r; }
-    for (uint64_t first = 0u; first < p->count; first += chunk) {
-        const auto n = std::min<uint64_t>(chunk, p->count - first);
-        LR_HIP_CHECK(hipMemcpyAsync(ctx->surface_hits.ptr, static_cast<const lrhip_ray_hit *>(p->hits) + first, n * sizeof(lrhip_ray_hit),
-                                    hipMemcpyHostToDevice, ctx->stream));
-        if (p->rays != nullptr) {
-            LR_HIP_CHECK(hipMemcpyAsync(ctx->raycast_rays.ptr, static_cast<const lrhip_ray *>(p->rays) + first, n * sizeof(lrhip_ray),
-                                        hipMemcpyHostToDevice, ctx->stream));
-        }
-        LR_HIP_CHECK(hipMemcpyAsync(ctx->bsdf_dirs.ptr, static_cast<const float4 *>(p->dirs) + first, n * sizeof(float4), hipMemcpyHostToDevice,
-                                    ctx->stream));
-        if (auto r = query_device(ctx, ctx->surface_hits.ptr, p->rays != nullptr ? ctx->raycast_rays.ptr : nullptr, ctx->bsdf_dirs.ptr, ctx->bsdf_out.ptr,
-                                  static_cast<uint32_t>(n), p->mode); r != LRHIP_OK) { return r; }
-        LR_HIP_CHECK(hipMemcpyAsync(static_cast<lrhip_bsdf_result *>(p->out) + first, ctx->bsdf_out.ptr, n * sizeof(lrhip_bsdf_result),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        LR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (auto r = collect_time(ctx); r != LRHIP_OK) { return r; }
-    }
-    return LRHIP_OK;
+    // the closures of the scene's surfaces themselves -- not ctx->features, which the volumetric integrator clears of them and the sibling
+    // integrators fill with all of them --, and what lrhip_set_diagnostics forces on top (the twin tests: a lean scene on the heavier kernels)
+    const auto features = ctx->closure_features | (ctx->diag_force_features & lrd::kFeatSceneMask);
+    return staged_call(ctx, ctx->bsdf_timer, p->count, device_pointers,
+                       {column_out(p->out, sizeof(lrhip_bsdf_result)), column_in(p->rays, sizeof(lrhip_ray)), column_in(p->hits, sizeof(lrhip_ray_hit)),
+                        column_in(p->dirs, sizeof(float4))},
+                       [&](uint32_t n, uint64_t, void *const *d) {
+        if (auto r = resident_meshes(ctx); r != LRHIP_OK) { return r; }
+        lrd::BsdfArgs args{};
+        fill_hit_table(ctx, args, d[2], d[1], n);
+        args.dirs = static_cast<const float4 *>(d[3]), args.out = static_cast<float4 *>(d[0]);
+        lrd::DScenePtr device_scene{};
+        if (auto r = upload_scene_record(ctx, device_scene); r != LRHIP_OK) { return r; }
+        if (auto r = timer_begin(ctx, ctx->bsdf_timer); r != LRHIP_OK) { return r; }
+        if (p->mode == LRHIP_BSDF_EVALUATE) { launch<lrd::kBsdfEvaluate>(features, blocks_of(n), ctx->stream, device_scene, args); }
+        else { launch<lrd::kBsdfSample>(features, blocks_of(n), ctx->stream, device_scene, args); }
+        LR_HIP_CHECK(hipGetLastError());
+        return timer_end(ctx, ctx->bsdf_timer);
+    });
 }
 
-double lrhip_last_bsdf_ms(lrhip_ctx *ctx) {
-    if (ctx == nullptr) { return 0.0; }
-    if (hipSetDevice(ctx->device) != hipSuccess || collect_time(ctx) != LRHIP_OK) { return -1.0; }
-    return ctx->bsdf_ms;
-}
+double lrhip_last_bsdf_ms(lrhip_ctx *ctx) { return ctx != nullptr ? timer_read(ctx, ctx->bsdf_timer) : 0.0; }
 
 }// extern "C"

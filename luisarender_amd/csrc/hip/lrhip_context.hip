@@ -121,29 +121,12 @@ void lrhip_destroy(lrhip_ctx *ctx) {
     ctx->denoise_guide.release(), ctx->denoise_colour[0].release(), ctx->denoise_colour[1].release(), ctx->denoise_inputs.release();
     if (ctx->denoise_begin) { (void)hipEventDestroy(ctx->denoise_begin); }
     if (ctx->denoise_end) { (void)hipEventDestroy(ctx->denoise_end); }
-    ctx->raycast_rays.release(), ctx->raycast_out.release();
-    if (ctx->raycast_begin) { (void)hipEventDestroy(ctx->raycast_begin); }
-    if (ctx->raycast_end) { (void)hipEventDestroy(ctx->raycast_end); }
-    ctx->radiance_streams.release(), ctx->radiance_out.release();
-    if (ctx->radiance_begin) { (void)hipEventDestroy(ctx->radiance_begin); }
-    if (ctx->radiance_end) { (void)hipEventDestroy(ctx->radiance_end); }
-    ctx->update_stage.release(), ctx->update_scratch.release();
-    if (ctx->update_begin) { (void)hipEventDestroy(ctx->update_begin); }
-    if (ctx->update_end) { (void)hipEventDestroy(ctx->update_end); }
-    if (ctx->mesh_begin) { (void)hipEventDestroy(ctx->mesh_begin); }
-    if (ctx->mesh_end) { (void)hipEventDestroy(ctx->mesh_end); }
-    ctx->surface_meshes.release(), ctx->surface_hits.release(), ctx->surface_out.release();
-    if (ctx->surface_begin) { (void)hipEventDestroy(ctx->surface_begin); }
-    if (ctx->surface_end) { (void)hipEventDestroy(ctx->surface_end); }
-    ctx->bsdf_dirs.release(), ctx->bsdf_out.release();
-    if (ctx->bsdf_begin) { (void)hipEventDestroy(ctx->bsdf_begin); }
-    if (ctx->bsdf_end) { (void)hipEventDestroy(ctx->bsdf_end); }
-    ctx->light_rays.release(), ctx->light_out.release();
-    if (ctx->light_begin) { (void)hipEventDestroy(ctx->light_begin); }
-    if (ctx->light_end) { (void)hipEventDestroy(ctx->light_end); }
-    ctx->camera_state.release(), ctx->camera_streams.release(), ctx->camera_indices.release(), ctx->camera_out.release();
-    if (ctx->camera_begin) { (void)hipEventDestroy(ctx->camera_begin); }
-    if (ctx->camera_end) { (void)hipEventDestroy(ctx->camera_end); }
+    for (auto &slot : ctx->staging) { slot.release(); }
+    for (auto timer : {&ctx->raycast_timer, &ctx->radiance_timer, &ctx->surface_timer, &ctx->bsdf_timer, &ctx->light_timer, &ctx->camera_timer,
+                       &ctx->instance_timer, &ctx->mesh_timer}) {
+        timer_destroy(*timer);
+    }
+    ctx->update_stage.release(), ctx->update_scratch.release(), ctx->surface_meshes.release();
     ctx->spill.release(), ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->wf_counts.release(), ctx->wf_accum.release();
     ctx->pool.release(), ctx->counters.release(), ctx->work_counter.release(), ctx->scene_record.release();
     if (ctx->ev_begin) { (void)hipEventDestroy(ctx->ev_begin); }

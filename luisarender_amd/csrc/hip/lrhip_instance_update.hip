@@ -51,32 +51,20 @@ lrd::InstanceUpdateArgs scene_args(lrhip_ctx *ctx) {
     return a;
 }
 
-// the kernels of one call over `count` matrices in device memory, between the context's update events
+// the kernels of one call over `count` matrices in device memory, between the events of the context's instance timer
 int update_device(lrhip_ctx *ctx, const void *matrices, const void *ids, uint32_t count) {
     if (ctx->update_counts[2] == 0u) { return LRHIP_OK; }// (every id is out of range)
     if (auto r = clear_update_scratch(ctx); r != LRHIP_OK) { return r; }
     auto a = scene_args(ctx);
     a.matrices = static_cast<const float4 *>(matrices), a.ids = static_cast<const uint32_t *>(ids), a.count = count;
     const dim3 block(lrd::kUpdateBlock);
-    LR_HIP_CHECK(hipEventRecord(ctx->update_begin, ctx->stream));
+    if (auto r = timer_begin(ctx, ctx->instance_timer); r != LRHIP_OK) { return r; }
     hipLaunchKernelGGL(lrd::instance_claim_kernel, dim3(blocks_for(count)), block, 0, ctx->stream, a);
     LR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(lrd::instance_record_kernel, dim3(blocks_for(count)), block, 0, ctx->stream, a);
     LR_HIP_CHECK(hipGetLastError());
     if (auto r = rebake_and_refit(ctx); r != LRHIP_OK) { return r; }
-    LR_HIP_CHECK(hipEventRecord(ctx->update_end, ctx->stream));
-    ctx->update_pending = true;
-    return LRHIP_OK;
-}
-
-int collect_time(lrhip_ctx *ctx) {
-    if (!ctx->update_pending) { return LRHIP_OK; }
-    float ms = 0.f;
-    LR_HIP_CHECK(hipEventSynchronize(ctx->update_end));
-    LR_HIP_CHECK(hipEventElapsedTime(&ms, ctx->update_begin, ctx->update_end));
-    ctx->update_ms = static_cast<double>(ms);
-    ctx->update_pending = false;
-    return LRHIP_OK;
+    return timer_end(ctx, ctx->instance_timer);
 }
 
 }// namespace
@@ -118,10 +106,7 @@ using namespace lrh;
 extern "C" {
 
 int lrhip_set_instance_transforms(lrhip_ctx *ctx, const lrhip_instance_update_params *p) {
-    if (ctx == nullptr || p == nullptr) { return fail(LRHIP_ERROR_INVALID, "lrhip_set_instance_transforms: NULL argument"); }
-    if ((p->flags & ~LRHIP_RAY_DEVICE_POINTERS) != 0u) { return fail(LRHIP_ERROR_INVALID, "lrhip_set_instance_transforms: unknown flags"); }
-    if (!ctx->scene_ready) { return fail(LRHIP_ERROR_INVALID, "lrhip_set_instance_transforms: no scene uploaded"); }
-    if (p->count > LRHIP_RAY_MAX_COUNT) { return fail(LRHIP_ERROR_INVALID, "lrhip_set_instance_transforms: more than 2^31 - 1 matrices"); }
+    if (auto r = screen("lrhip_set_instance_transforms", ctx, p, LRHIP_RAY_DEVICE_POINTERS, "matrices"); r != LRHIP_OK) { return r; }
     const auto instance_count = ctx->update_counts[2];
     if (p->instances == nullptr && p->count > instance_count) {
         return fail(LRHIP_ERROR_INVALID, "lrhip_set_instance_transforms: " + std::to_string(p->count) + " matrices without ids for " +
@@ -131,7 +116,7 @@ int lrhip_set_instance_transforms(lrhip_ctx *ctx, const lrhip_instance_update_pa
     const auto device_pointers = (p->flags & LRHIP_RAY_DEVICE_POINTERS) != 0u;
     const auto count = static_cast<uint32_t>(p->count);
     if (device_pointers && count != 0u) {
-        if ((reinterpret_cast<uintptr_t>(p->object_to_world) & 15u) != 0u || (reinterpret_cast<uintptr_t>(p->instances) & 3u) != 0u) {
+        if (misaligned({{p->object_to_world, 15u}, {p->instances, 3u}})) {
             return fail(LRHIP_ERROR_INVALID, "lrhip_set_instance_transforms: device matrices must be 16-byte aligned, device ids 4-byte aligned");
         }
     }
@@ -159,11 +144,8 @@ int lrhip_set_instance_transforms(lrhip_ctx *ctx, const lrhip_instance_update_pa
     if (count != 0u && ctx->level_offsets.empty()) {
         return fail(LRHIP_ERROR_UNSUPPORTED, "lrhip_set_instance_transforms: the BVH's nodes are not stored parents first; it cannot be refitted in place");
     }
-    LR_HIP_CHECK(hipSetDevice(ctx->device));
-    ctx->update_ms = 0.0, ctx->update_pending = false;
+    if (auto r = timer_start(ctx, ctx->instance_timer, count != 0u); r != LRHIP_OK) { return r; }
     if (count == 0u) { return LRHIP_OK; }
-    if (ctx->update_begin == nullptr) { LR_HIP_CHECK(hipEventCreate(&ctx->update_begin)); }
-    if (ctx->update_end == nullptr) { LR_HIP_CHECK(hipEventCreate(&ctx->update_end)); }
     if (device_pointers) { return update_device(ctx, p->object_to_world, p->instances, count); }
     // host pointers: matrices, then ids, through the staging buffer
     const auto matrix_bytes = static_cast<size_t>(count) * 16u * sizeof(float), id_bytes = static_cast<size_t>(count) * sizeof(uint32_t);
@@ -173,14 +155,10 @@ int lrhip_set_instance_transforms(lrhip_ctx *ctx, const lrhip_instance_update_pa
     if (p->instances != nullptr) { LR_HIP_CHECK(hipMemcpyAsync(staged_ids, p->instances, id_bytes, hipMemcpyHostToDevice, ctx->stream)); }
     if (auto r = update_device(ctx, ctx->update_stage.ptr, p->instances != nullptr ? staged_ids : nullptr, count); r != LRHIP_OK) { return r; }
     LR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return collect_time(ctx);
+    return timer_collect(ctx->instance_timer, false);
 }
 
-double lrhip_last_instance_update_ms(lrhip_ctx *ctx) {
-    if (ctx == nullptr) { return 0.0; }
-    if (hipSetDevice(ctx->device) != hipSuccess || collect_time(ctx) != LRHIP_OK) { return -1.0; }
-    return ctx->update_ms;
-}
+double lrhip_last_instance_update_ms(lrhip_ctx *ctx) { return ctx != nullptr ? timer_read(ctx, ctx->instance_timer, false) : 0.0; }
 
 uint64_t lrhip_scene_table_bytes(lrhip_ctx *ctx, uint32_t which) {
     const void *base = nullptr;

@@ -8,6 +8,7 @@
 //   lrhip_wavefront.hip  the host loop of wavefront mode
 //   lrhip_comm.hip       the RCCL collectives
 //   lrhip_denoise.hip    the edge-avoiding wavelet filter over the AOV buffers (denoise_kernels.h)
+//   lrhip_query.hip      what the queries and the device updates share on the host: screening, timers, the scene record, staging
 //   lrhip_raycast.hip    ray queries: closest hit / occlusion for caller-supplied rays (raycast_kernel.h)
 //   lrhip_radiance.hip   radiance queries: MegaPath's estimator along caller-supplied rays (the kFeatQuery kernels of megapath_kernel.h)
 //   lrhip_surface.hip    surface queries: position, normals, uv, material and emission at caller-supplied hits (surface_kernel.h)
@@ -26,11 +27,14 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <functional>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "megapath_kernel.h"
 #include "megapool_kernel.h"
+#include "query_columns.h"
 #include "variants.h"
 
 namespace lrh {
@@ -54,6 +58,16 @@ struct DeviceBuffer {
     }
 };
 int ensure(DeviceBuffer &b, size_t bytes);// grows, never shrinks; the contents are lost when it grows
+
+// the kernel time of a family's last call (lrhip_query.hip): events around the last launch, made on first use; the time of the call's
+// finished launches; whether a launch is still to be read
+struct Timer {
+    hipEvent_t begin{nullptr}, end{nullptr};
+    double ms{0.};
+    bool pending{false};
+};
+// staging slots of a host-pointer call, one per column of the widest call (staged_call)
+constexpr uint32_t kQuerySlots = 5u;
 
 // persistent-grid sizing inputs that must not depend on the device actually present, so that the
 // chunking (and therefore the fp32 summation order of the film) is identical on every GPU
@@ -166,87 +180,87 @@ struct lrhip_ctx {
     lrh::DeviceBuffer denoise_guide, denoise_colour[2], denoise_inputs;
     hipEvent_t denoise_begin{nullptr}, denoise_end{nullptr};// around the kernels of the last call (lrhip_last_denoise_ms); made on first use
     bool denoise_timed{false};
-    // ray queries (lrhip_raycast.hip): the staging buffers of a host-pointer call (one chunk of rays, one of results; they grow on demand
-    // and outlive the scene), the events around the last launch, the kernel time of the last call's finished launches and whether one is
-    // still to be read (lrhip_last_trace_ms), resident blocks per CU of the two kernels (alpha test off / on; -1: not asked yet)
-    lrh::DeviceBuffer raycast_rays, raycast_out;
-    hipEvent_t raycast_begin{nullptr}, raycast_end{nullptr};
-    double raycast_ms{0.};
-    bool raycast_pending{false};
-    int raycast_blocks[2]{-1, -1};
-    // radiance queries (lrhip_radiance.hip): a host-pointer call stages its rays through raycast_rays above, its stream ids and records through
-    // these two (they grow on demand and outlive the scene); the events around the last launch, the kernel time of the last call's finished
-    // launches and whether one is still to be read (lrhip_last_radiance_ms).  The chunks' partial planes are `partial`, the film kernels' own
-    lrh::DeviceBuffer radiance_streams, radiance_out;
-    hipEvent_t radiance_begin{nullptr}, radiance_end{nullptr};
-    double radiance_ms{0.};
-    bool radiance_pending{false};
+    // The queries and the device updates (lrhip_query.hip).  `staging`: the slots of a host-pointer call, column i of the call in slot i
+    // (staged_call); they grow on demand and outlive the scene.  NOTHING STAGED OUTLIVES A CALL: every host-pointer call synchronises per
+    // chunk, so a slot is free for whichever call comes next.  The calls list their columns in one order -- 0 the result, 1 rays or sampler
+    // states, 2 hit records or ids, 3 numbers or sample indices, 4 rays written -- which is what bounds the slots' sizes.
+    // One timer per family (lrhip_last_*_ms)
+    lrh::DeviceBuffer staging[lrh::kQuerySlots];
+    lrh::Timer raycast_timer, radiance_timer, surface_timer, bsdf_timer, light_timer, camera_timer, instance_timer, mesh_timer;
+    int raycast_blocks[2]{-1, -1};// ray queries: resident blocks per CU of the two kernels (alpha test off / on; -1: not asked yet)
     // moving instances (lrhip_instance_update.hip).  Of the uploaded scene (in scene_buffers): the fp32 boxes of the BVH the packets are
     // quantised from, refitted in place, and the node indices sorted by level of the tree -- level l is level_nodes[level_offsets[l] ..
     // level_offsets[l + 1]); empty level_offsets: the node order does not allow a refit (a child before its parent).  Of the context: the
-    // staging buffer of a host-pointer call (matrices, then ids), the call's scratch (owner word per instance, then the moved-instance
-    // bits), the events around the last call's kernels, and its kernel time once read (lrhip_last_instance_update_ms)
+    // staging buffer of a host-pointer call (matrices, then ids) and the call's scratch (owner word per instance, then the moved-instance
+    // bits)
     lr_bvh4_node *nodes32{nullptr};
     const uint32_t *level_nodes{nullptr};
     std::vector<uint32_t> level_offsets;
     uint64_t vertex_count{0u};
     lrh::DeviceBuffer update_stage, update_scratch;
-    hipEvent_t update_begin{nullptr}, update_end{nullptr};
-    double update_ms{0.};
-    bool update_pending{false};
     // deforming a mesh (lrhip_mesh_update.hip).  Of the uploaded scene: a host copy of the lr_mesh table, per mesh the first instance that
     // carries a light (LR_INVALID_ID: none -- an emitter's vertices are not moved), and per mesh the corner lists of the normal recompute in
-    // device memory, built on first use and released with the scene.  Of the context: the events around the last call's kernels and its
-    // kernel time once read (lrhip_last_mesh_update_ms).  Staging buffer and scratch are the instance call's
+    // device memory, built on first use and released with the scene.  Staging buffer and scratch are the instance call's
     std::vector<lr_mesh> meshes;
     std::vector<uint32_t> mesh_light;
     std::vector<lrh::DeviceBuffer> mesh_adjacency;
-    hipEvent_t mesh_begin{nullptr}, mesh_end{nullptr};
-    double mesh_ms{0.};
-    bool mesh_pending{false};
-    // surface queries (lrhip_surface.hip).  Of the uploaded scene: the lr_mesh table in device memory (what bounds `prim` of a record that
-    // names an instance), copied on the first query after an upload (surface_meshes_ready; release_scene clears it).  Of the context: the
-    // staging buffers of a host-pointer call (hit records, results; the rays go through raycast_rays) -- they grow on demand and outlive the
-    // scene --, the events around the last launch, the kernel time of the last call's finished launches and whether one is still to be read
-    // (lrhip_last_surface_ms)
-    lrh::DeviceBuffer surface_meshes, surface_hits, surface_out;
+    // surface, BSDF and light queries.  Of the uploaded scene: the lr_mesh table in device memory (what bounds `prim` of a record that names
+    // an instance), copied on the first such query after an upload (resident_meshes; release_scene clears the flag), and the kFeatDisney /
+    // kFeatMix / kFeatLayered bits of its surfaces THEMSELVES, whatever the integrator (`features` above is what the renderer's kernel must
+    // hold: the sibling integrators set every closure bit in it and the volumetric one clears them) -- what picks the BSDF query's kernel
+    lrh::DeviceBuffer surface_meshes;
     bool surface_meshes_ready{false};
-    hipEvent_t surface_begin{nullptr}, surface_end{nullptr};
-    double surface_ms{0.};
-    bool surface_pending{false};
-    // BSDF queries (lrhip_bsdf.hip).  Of the uploaded scene: the kFeatDisney / kFeatMix / kFeatLayered bits of its surfaces THEMSELVES,
-    // whatever the integrator (`features` above is what the renderer's kernel must hold: the sibling integrators set every closure bit in
-    // it and the volumetric one clears them) -- what picks the query's kernel.  Of the context: the staging buffers of a host-pointer call
-    // (dirs, results; the hit records go through surface_hits and the rays through raycast_rays) -- they grow on demand and outlive the
-    // scene --, the events around the last launch, the kernel time of the last call's finished launches and whether one is still to be
-    // read (lrhip_last_bsdf_ms).  The lr_mesh table is the surface queries' (surface_meshes)
     uint32_t closure_features{0u};
-    lrh::DeviceBuffer bsdf_dirs, bsdf_out;
-    hipEvent_t bsdf_begin{nullptr}, bsdf_end{nullptr};
-    double bsdf_ms{0.};
-    bool bsdf_pending{false};
-    // light queries (lrhip_light.hip).  Of the context: the staging buffers of a host-pointer call's results (shadow rays, records; hit records or
-    // points go through surface_hits, the rays through raycast_rays, the random numbers through bsdf_dirs) -- they grow on demand and
-    // outlive the scene --, the events around the last launch, the kernel time of the last call's finished launches and whether one is
-    // still to be read (lrhip_last_light_ms).  The lr_mesh table is the surface queries' (surface_meshes)
-    lrh::DeviceBuffer light_rays, light_out;
-    hipEvent_t light_begin{nullptr}, light_end{nullptr};
-    double light_ms{0.};
-    bool light_pending{false};
-    // camera, sampler and film queries (lrhip_camera.hip).  Of the context: the staging buffers of a host-pointer call -- sampler states (the camera
-    // query's 16-byte records go through the same buffer), stream or pixel ids, sample indices, the drawn numbers; the caller's numbers and values go
-    // through bsdf_dirs, the camera rays through light_rays -- they grow on demand and outlive the scene --, the events around the last launch, the
-    // kernel time of the last call's finished launches and whether one is still to be read (lrhip_last_camera_ms)
-    lrh::DeviceBuffer camera_state, camera_streams, camera_indices, camera_out;
-    hipEvent_t camera_begin{nullptr}, camera_end{nullptr};
-    double camera_ms{0.};
-    bool camera_pending{false};
 };
 
 namespace lrh {
 
 // resident blocks per CU of `entry` (asked once per upload, at most kMaxBlocksPerCu); `lds_bytes`: the launch's dynamic LDS
 int kernel_blocks(lrhip_ctx *ctx, const KernelEntry &entry, unsigned lds_bytes, uint32_t &blocks_per_cu);
+
+// ---- lrhip_query.hip: the one host path of the queries and the device updates
+// A call's timer.  timer_start: the device, a call's time of zero, and the events if the call will launch.  timer_begin / timer_end: around a
+// launch on the context's stream.  timer_collect: the pending launch's time joins the call's (synchronises with it); `sum`: the call adds
+// its launches up (the queries), or keeps the last one (the updates).  timer_read: the whole body of a lrhip_last_*_ms
+int timer_start(lrhip_ctx *ctx, Timer &t, bool launches);
+int timer_begin(lrhip_ctx *ctx, Timer &t);
+int timer_end(lrhip_ctx *ctx, Timer &t);
+int timer_collect(Timer &t, bool sum = true);
+double timer_read(lrhip_ctx *ctx, Timer &t, bool sum = true);
+void timer_destroy(Timer &t);
+// What every call checks first, in this order: NULL context or parameters, flags outside `allowed_flags`, more than LRHIP_RAY_MAX_COUNT
+// `noun` (nullptr: the call bounds its count itself), no scene uploaded
+int screen_call(const char *name, const lrhip_ctx *ctx, const void *params, uint32_t flags, uint32_t allowed_flags, uint64_t count, const char *noun);
+template<typename Params>
+int screen(const char *name, const lrhip_ctx *ctx, const Params *p, uint32_t allowed_flags, const char *noun) {
+    return screen_call(name, ctx, p, p != nullptr ? p->flags : 0u, allowed_flags, p != nullptr ? p->count : 0u, noun);
+}
+struct PointerMask {
+    const void *pointer;
+    uintptr_t mask;// 15: 16-byte aligned, 3: 4-byte
+};
+bool misaligned(std::initializer_list<PointerMask> pointers);// (NULL is aligned)
+// ctx->scene, or the caller's modified copy of it, into ctx->scene_record on the context's stream
+int upload_scene_record(lrhip_ctx *ctx, lrd::DScenePtr &device_scene, const lrd::DScene *record = nullptr);
+int resident_meshes(lrhip_ctx *ctx);// the lr_mesh table of the uploaded scene in ctx->surface_meshes: copied once per upload
+// what the surface, BSDF and light kernels' arguments share: the hit records, the rays, the tables that bound a record's ids
+template<typename Args>
+void fill_hit_table(const lrhip_ctx *ctx, Args &args, const void *hits, const void *rays, uint32_t count) {
+    args.hits = static_cast<const float4 *>(hits), args.rays = static_cast<const float4 *>(rays);
+    args.meshes = static_cast<const lr_mesh *>(ctx->surface_meshes.ptr);
+    args.count = count;
+    args.triangle_count = ctx->update_counts[1], args.instance_count = ctx->update_counts[2];
+    args.mesh_count = static_cast<uint32_t>(ctx->meshes.size());
+}
+// blocks of a one-lane-per-record launch: 2^20 blocks of 256 lanes cover 2^28 records in one pass; a larger batch strides
+constexpr uint32_t kQueryMaxBlocks = 1u << 20u;
+inline uint32_t blocks_of(uint32_t count) { return std::min(kQueryMaxBlocks, (count + lrd::kBlockThreads - 1u) / lrd::kBlockThreads); }
+// One call over `count` records, column i of `columns` through ctx->staging[i].  launch(n, first, pointers): one launch over records
+// [first, first + n) whose column i is at device address pointers[i] (nullptr: absent), between timer_begin and timer_end of `timer`.
+// Device pointers: one launch over the caller's arrays.  Host pointers: per chunk of kQueryChunk records the copies in, the launch, the
+// copies out, a synchronise and timer_collect
+using QueryLaunch = std::function<int(uint32_t n, uint64_t first, void *const *pointers)>;
+int staged_call(lrhip_ctx *ctx, Timer &timer, uint64_t count, bool device_pointers, std::initializer_list<Column> columns, const QueryLaunch &launch);
 
 void release_scene(lrhip_ctx *ctx);// frees the uploaded scene's buffers and what is sized for it (queues, pool records)
 

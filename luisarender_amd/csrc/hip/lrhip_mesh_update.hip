@@ -12,8 +12,6 @@ namespace lrh {
 
 namespace {
 
-constexpr auto kWhat = "lrhip_set_mesh_vertices: ";
-
 unsigned blocks_for(uint64_t threads) { return static_cast<unsigned>((threads + lrd::kMeshUpdateBlock - 1u) / lrd::kMeshUpdateBlock); }
 
 // The corner lists of mesh `m` (mesh_update_kernels.h: offsets, then corners, in one buffer), built on the first call that recomputes the
@@ -51,7 +49,7 @@ int ensure_adjacency(lrhip_ctx *ctx, uint32_t m) {
     return LRHIP_OK;
 }
 
-// the kernels of one call over `count` vertices in device memory, between the context's mesh-update events
+// the kernels of one call over `count` vertices in device memory, between the events of the context's mesh timer
 int update_device(lrhip_ctx *ctx, const lrhip_mesh_update_params *p, const void *positions, const void *normals) {
     const auto &d = ctx->scene;
     const auto &mesh = ctx->meshes[p->mesh];
@@ -74,7 +72,7 @@ int update_device(lrhip_ctx *ctx, const lrhip_mesh_update_params *p, const void 
     if (auto r = clear_update_scratch(ctx); r != LRHIP_OK) { return r; }
     a.moved = update_moved_mask(ctx);
     const dim3 block(lrd::kMeshUpdateBlock);
-    LR_HIP_CHECK(hipEventRecord(ctx->mesh_begin, ctx->stream));
+    if (auto r = timer_begin(ctx, ctx->mesh_timer); r != LRHIP_OK) { return r; }
     hipLaunchKernelGGL(lrd::mesh_vertex_kernel, dim3(blocks_for(a.count)), block, 0, ctx->stream, a);
     LR_HIP_CHECK(hipGetLastError());
     if (recompute && mesh.vertex_count != 0u) {
@@ -86,19 +84,7 @@ int update_device(lrhip_ctx *ctx, const lrhip_mesh_update_params *p, const void 
         LR_HIP_CHECK(hipGetLastError());
     }
     if (auto r = rebake_and_refit(ctx); r != LRHIP_OK) { return r; }
-    LR_HIP_CHECK(hipEventRecord(ctx->mesh_end, ctx->stream));
-    ctx->mesh_pending = true;
-    return LRHIP_OK;
-}
-
-int collect_time(lrhip_ctx *ctx) {
-    if (!ctx->mesh_pending) { return LRHIP_OK; }
-    float ms = 0.f;
-    LR_HIP_CHECK(hipEventSynchronize(ctx->mesh_end));
-    LR_HIP_CHECK(hipEventElapsedTime(&ms, ctx->mesh_begin, ctx->mesh_end));
-    ctx->mesh_ms = static_cast<double>(ms);
-    ctx->mesh_pending = false;
-    return LRHIP_OK;
+    return timer_end(ctx, ctx->mesh_timer);
 }
 
 }// namespace
@@ -110,10 +96,9 @@ using namespace lrh;
 extern "C" {
 
 int lrhip_set_mesh_vertices(lrhip_ctx *ctx, const lrhip_mesh_update_params *p) {
-    const std::string what{kWhat};
-    if (ctx == nullptr || p == nullptr) { return fail(LRHIP_ERROR_INVALID, what + "NULL argument"); }
-    if ((p->flags & ~(LRHIP_RAY_DEVICE_POINTERS | LRHIP_MESH_RECOMPUTE_NORMALS)) != 0u) { return fail(LRHIP_ERROR_INVALID, what + "unknown flags"); }
-    if (!ctx->scene_ready) { return fail(LRHIP_ERROR_INVALID, what + "no scene uploaded"); }
+    // (no count screened: a mesh's vertex count bounds it below)
+    if (auto r = screen("lrhip_set_mesh_vertices", ctx, p, LRHIP_RAY_DEVICE_POINTERS | LRHIP_MESH_RECOMPUTE_NORMALS, nullptr); r != LRHIP_OK) { return r; }
+    const std::string what{"lrhip_set_mesh_vertices: "};
     if (p->mesh >= ctx->meshes.size()) {
         return fail(LRHIP_ERROR_INVALID, what + "mesh " + std::to_string(p->mesh) + " out of range (" + std::to_string(ctx->meshes.size()) + " meshes)");
     }
@@ -136,7 +121,7 @@ int lrhip_set_mesh_vertices(lrhip_ctx *ctx, const lrhip_mesh_update_params *p) {
     const auto device_pointers = (p->flags & LRHIP_RAY_DEVICE_POINTERS) != 0u;
     const auto floats = static_cast<size_t>(p->count) * 3u;
     if (device_pointers && p->count != 0u) {
-        if (((reinterpret_cast<uintptr_t>(p->positions) | reinterpret_cast<uintptr_t>(p->normals)) & 3u) != 0u) {
+        if (misaligned({{p->positions, 3u}, {p->normals, 3u}})) {
             return fail(LRHIP_ERROR_INVALID, what + "device positions and normals must be 4-byte aligned");
         }
     }
@@ -153,11 +138,8 @@ int lrhip_set_mesh_vertices(lrhip_ctx *ctx, const lrhip_mesh_update_params *p) {
     if (p->count != 0u && ctx->level_offsets.empty()) {
         return fail(LRHIP_ERROR_UNSUPPORTED, what + "the BVH's nodes are not stored parents first; it cannot be refitted in place");
     }
-    LR_HIP_CHECK(hipSetDevice(ctx->device));
-    ctx->mesh_ms = 0.0, ctx->mesh_pending = false;
+    if (auto r = timer_start(ctx, ctx->mesh_timer, p->count != 0u); r != LRHIP_OK) { return r; }
     if (p->count == 0u) { return LRHIP_OK; }
-    if (ctx->mesh_begin == nullptr) { LR_HIP_CHECK(hipEventCreate(&ctx->mesh_begin)); }
-    if (ctx->mesh_end == nullptr) { LR_HIP_CHECK(hipEventCreate(&ctx->mesh_end)); }
     if (device_pointers) { return update_device(ctx, p, p->positions, p->normals); }
     // host pointers: positions, then normals, through the staging buffer
     const auto bytes = floats * sizeof(float);
@@ -167,13 +149,9 @@ int lrhip_set_mesh_vertices(lrhip_ctx *ctx, const lrhip_mesh_update_params *p) {
     if (p->normals != nullptr) { LR_HIP_CHECK(hipMemcpyAsync(staged_normals, p->normals, bytes, hipMemcpyHostToDevice, ctx->stream)); }
     if (auto r = update_device(ctx, p, ctx->update_stage.ptr, p->normals != nullptr ? staged_normals : nullptr); r != LRHIP_OK) { return r; }
     LR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return collect_time(ctx);
+    return timer_collect(ctx->mesh_timer, false);
 }
 
-double lrhip_last_mesh_update_ms(lrhip_ctx *ctx) {
-    if (ctx == nullptr) { return 0.0; }
-    if (hipSetDevice(ctx->device) != hipSuccess || collect_time(ctx) != LRHIP_OK) { return -1.0; }
-    return ctx->mesh_ms;
-}
+double lrhip_last_mesh_update_ms(lrhip_ctx *ctx) { return ctx != nullptr ? timer_read(ctx, ctx->mesh_timer, false) : 0.0; }
 
 }// extern "C"

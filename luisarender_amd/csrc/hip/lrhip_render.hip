@@ -228,12 +228,11 @@ int lrhip_render(lrhip_ctx *ctx, const lrhip_render_params *p) {
     // how this launch's kernel counts its samples, set on EVERY path (the field lives in ctx->scene and used to keep whatever the
     // last pool / wavefront call left in it): a pool kernel counts an item's samples when its wave leaves the item, the others where they finish
     ctx->scene.wf.count_at_flush = pool ? 1u : 0u;
-    // the scene record of THIS launch (shutter weight, film clamp, ...) in stream order; ctx->scene is pageable host memory, so
-    // the copy has left it when the call returns
-    if (auto r = ensure(ctx->scene_record, sizeof(lrd::DScene)); r != LRHIP_OK) { return r; }
-    LR_HIP_CHECK(hipMemcpyAsync(ctx->scene_record.ptr, &ctx->scene, sizeof(lrd::DScene), hipMemcpyHostToDevice, ctx->stream));
+    // the scene record of THIS launch (shutter weight, film clamp, ...) in stream order
+    lrd::DScenePtr device_scene{};
+    if (auto r = upload_scene_record(ctx, device_scene); r != LRHIP_OK) { return r; }
     if (!ctx->in_split) { LR_HIP_CHECK(hipEventRecord(ctx->ev_begin, ctx->stream)); }
-    LR_HIP_CHECK(entry->launch(blocks, ctx->stream, static_cast<const lrd::DScene *>(ctx->scene_record.ptr), &args, lds_bytes));
+    LR_HIP_CHECK(entry->launch(blocks, ctx->stream, (const lrd::DScene *)device_scene, &args, lds_bytes));
     ctx->last_variant = entry->mask;
     LR_HIP_CHECK(hipGetLastError());
     LR_HIP_CHECK(hipEventRecord(ctx->ev_end, ctx->stream));

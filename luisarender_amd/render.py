@@ -593,6 +593,37 @@ class CameraRays:
         return int(self.buffer.shape[0])
 
 
+class _Arrays:
+    """The arrays of one library call: numpy (host pointers, the call synchronises) or torch on the renderer's GPU (device pointers)."""
+
+    def __init__(self, kind: str, device: int):
+        self.torch = kind == "torch"
+        self.device = device
+        self.padded = False  # a padding copy was made on torch's stream
+
+    def empty(self, shape, dtype=np.float32):
+        if not self.torch:
+            return np.empty(shape, dtype)
+        import torch
+        return torch.empty(shape, dtype=torch.int32 if dtype == np.uint32 else torch.float32, device=torch.device("cuda", self.device))
+
+    def pad(self, a, width: int, value: float = 0.0):
+        """[N, w] -> [N, width]: the columns the caller left out hold `value`"""
+        missing = width - a.shape[1]
+        if missing == 0:
+            return a
+        if not self.torch:
+            return np.concatenate([a, np.full((a.shape[0], missing), value, np.float32)], axis=1)
+        import torch
+        self.padded = True
+        return torch.nn.functional.pad(a, (0, missing), value=value).contiguous()
+
+    def ptr(self, a):
+        if a is None:
+            return None
+        return a.data_ptr() if self.torch else a.ctypes.data
+
+
 class MegaPathRenderer:
     """One lrhip_ctx on one GPU.  Mirrors the reference's ProgressiveIntegrator::Instance::render
     (src/base/integrator.cpp:34-49): prepare film -> render spp -> download (convert) -> save."""
@@ -609,6 +640,19 @@ class MegaPathRenderer:
     def _check(self, rc: int) -> None:
         if rc != 0:
             raise DeviceError(f"lrhip error {rc}: {self._lib.lrhip_last_error().decode()}")
+
+    def _call(self, function, p, a: _Arrays, sync: bool, wait_after: bool = True) -> None:
+        # One call over the arrays of `a`.  torch: device pointers; torch's current stream is synchronised before the call if `sync`, or if a
+        # padding copy runs on it (the call runs on the context's stream), and the context after it for the same reasons (the copy must outlive
+        # the kernel that reads it).  wait_after=False: the call stays asynchronous on the context's stream
+        if a.torch:
+            import torch
+            p.flags |= _ffi.RAY_DEVICE_POINTERS
+            if sync or a.padded:
+                torch.cuda.current_stream(torch.device("cuda", a.device)).synchronize()
+        self._check(function(self._ctx, C.byref(p)))
+        if a.torch and wait_after and (sync or a.padded):
+            self.synchronize()
 
     def set_stream(self, hip_stream: int | None) -> None:
         self._check(self._lib.lrhip_set_stream(self._ctx, C.c_void_p(hip_stream or 0)))
@@ -726,26 +770,15 @@ class MegaPathRenderer:
         renderer's GPU is read in place and the result is a tensor on that device, without a copy through the host: torch's current
         stream is synchronised before the call and the context after it; a caller who has bound the context to torch's stream
         (set_stream) may pass sync=False.  Returns RayHits, or with any_hit a bool array / tensor [N] (True: occluded)."""
-        kind = check_rays(rays, self._device)
+        a = _Arrays(check_rays(rays, self._device), self._device)
         n = int(rays.shape[0])
         p = _ffi.RayQueryParams()
         p.count = n
         p.mode = _ffi.RAY_ANY if any_hit else _ffi.RAY_CLOSEST
         p.flags = _ffi.RAY_ALPHA_TEST if alpha_test else 0
-        if kind == "numpy":
-            out = np.empty(n, np.uint32) if any_hit else np.empty((n, 8), np.float32)
-            p.rays, p.out = rays.ctypes.data, out.ctypes.data
-            self._check(self._lib.lrhip_trace_rays(self._ctx, C.byref(p)))
-            return out != 0 if any_hit else RayHits(out)
-        import torch
-        out = torch.empty(n, dtype=torch.int32, device=rays.device) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=rays.device)
-        p.rays, p.out = rays.data_ptr(), out.data_ptr()
-        p.flags |= _ffi.RAY_DEVICE_POINTERS
-        if sync:
-            torch.cuda.current_stream(rays.device).synchronize()
-        self._check(self._lib.lrhip_trace_rays(self._ctx, C.byref(p)))
-        if sync:
-            self.synchronize()
+        out = a.empty(n, np.uint32) if any_hit else a.empty((n, 8))
+        p.rays, p.out = a.ptr(rays), a.ptr(out)
+        self._call(self._lib.lrhip_trace_rays, p, a, sync)
         return out != 0 if any_hit else RayHits(out)
 
     def last_trace_ms(self) -> float:
@@ -760,32 +793,24 @@ class MegaPathRenderer:
         streams: the sampler stream of each ray (None: 0, 1, 2, ...; stream py * W + px is pixel (px, py)'s).  clamp: per-sample clamp (None:
         the scene's film clamp).  accumulate_into: a previous raw result, refined IN PLACE by these samples and returned.  Returns the [N, 3]
         means sum / max(n, 1), or with raw the [N, 4] sums (sum r, sum g, sum b, n).  counters: the counting kernel (counters())."""
-        kind = check_radiance_args(rays, spp, spp_begin, streams, clamp, accumulate_into, self._device)
+        a = _Arrays(check_radiance_args(rays, spp, spp_begin, streams, clamp, accumulate_into, self._device), self._device)
         n = int(rays.shape[0])
         p = _ffi.RadianceQueryParams()
         p.count = n
         p.spp_begin, p.spp_end = spp_begin, spp_begin + spp
         p.clamp = 0.0 if clamp is None else clamp
         p.flags = (_ffi.RADIANCE_ACCUMULATE if accumulate_into is not None else 0) | (_ffi.RADIANCE_COUNTERS if counters else 0)
-        if kind == "numpy":
-            out = accumulate_into if accumulate_into is not None else np.empty((n, 4), np.float32)
-            p.rays, p.out = rays.ctypes.data, out.ctypes.data
-            p.streams = streams.ctypes.data if streams is not None else None
-            self._check(self._lib.lrhip_trace_radiance(self._ctx, C.byref(p)))
-            return out if raw else out[:, :3] / np.maximum(out[:, 3:4], np.float32(1.0))
-        import torch
-        out = accumulate_into if accumulate_into is not None else torch.empty((n, 4), dtype=torch.float32, device=rays.device)
-        if n != 0 and (rays.data_ptr() % 16 != 0 or out.data_ptr() % 16 != 0):
+        out = accumulate_into if accumulate_into is not None else a.empty((n, 4))
+        p.rays, p.out, p.streams = a.ptr(rays), a.ptr(out), a.ptr(streams)
+        if a.torch and n != 0 and (p.rays % 16 != 0 or p.out % 16 != 0):
             raise ValueError("radiance: rays and accumulate_into must be 16-byte aligned on the device")
-        p.rays, p.out = rays.data_ptr(), out.data_ptr()
-        p.streams = streams.data_ptr() if streams is not None else None
-        p.flags |= _ffi.RAY_DEVICE_POINTERS
-        if sync:
-            torch.cuda.current_stream(rays.device).synchronize()
-        self._check(self._lib.lrhip_trace_radiance(self._ctx, C.byref(p)))
-        if sync:
-            self.synchronize()
-        return out if raw else out[:, :3] / torch.clamp(out[:, 3:4], min=1.0)
+        self._call(self._lib.lrhip_trace_radiance, p, a, sync)
+        if raw:
+            return out
+        if a.torch:
+            import torch
+            return out[:, :3] / torch.clamp(out[:, 3:4], min=1.0)
+        return out[:, :3] / np.maximum(out[:, 3:4], np.float32(1.0))
 
     def last_radiance_ms(self) -> float:
         """lrhip_last_radiance_ms: HIP-event time of the kernel(s) of the last radiance()"""
@@ -798,31 +823,20 @@ class MegaPathRenderer:
         viewing rays (emission and back_facing are taken from them), or None: every point is seen from its front.  geometry_only: material and
         emission are skipped (zeros) -- this form serves every scene.  numpy arrays go through host pointers; torch tensors on this renderer's
         GPU are read in place and the result stays on the device (synchronisation as in trace())."""
-        kind = check_surface_args(hits, rays, self._device)
-        if kind == "torch" and sync:
-            import torch
-            torch.cuda.current_stream((rays if rays is not None else getattr(hits, "buffer", hits)).device).synchronize()
+        a = _Arrays(check_surface_args(hits, rays, self._device), self._device)
         if hits is None:  # (the trace and the query are ordered on the context's stream: no host round trip between them)
-            hits = self.trace(rays, sync=False) if kind == "torch" else self.trace(rays)
+            if a.torch and sync:
+                import torch
+                torch.cuda.current_stream(rays.device).synchronize()
+            hits = self.trace(rays, sync=False)
         buffer = hits.buffer if isinstance(hits, RayHits) else hits
         n = int(buffer.shape[0])
         p = _ffi.SurfaceQueryParams()
         p.count = n
         p.flags = _ffi.SURFACE_GEOMETRY_ONLY if geometry_only else 0
-        if kind == "numpy":
-            out = np.empty((n, 32), np.float32)
-            p.hits, p.out = buffer.ctypes.data, out.ctypes.data
-            p.rays = rays.ctypes.data if rays is not None else None
-            self._check(self._lib.lrhip_query_surface(self._ctx, C.byref(p)))
-            return SurfacePoints(out)
-        import torch
-        out = torch.empty((n, 32), dtype=torch.float32, device=buffer.device)
-        p.hits, p.out = buffer.data_ptr(), out.data_ptr()
-        p.rays = rays.data_ptr() if rays is not None else None
-        p.flags |= _ffi.RAY_DEVICE_POINTERS
-        self._check(self._lib.lrhip_query_surface(self._ctx, C.byref(p)))
-        if sync:
-            self.synchronize()
+        out = a.empty((n, 32))
+        p.hits, p.rays, p.out = a.ptr(buffer), a.ptr(rays), a.ptr(out)
+        self._call(self._lib.lrhip_query_surface, p, a, sync)
         return SurfacePoints(out)
 
     def last_surface_ms(self) -> float:
@@ -830,32 +844,14 @@ class MegaPathRenderer:
         return float(self._lib.lrhip_last_surface_ms(self._ctx))
 
     def _bsdf(self, mode: int, hits, dirs, rays, sync: bool, what: str) -> BsdfResults:
-        kind = check_bsdf_args(hits, dirs, rays, self._device, what)
+        a = _Arrays(check_bsdf_args(hits, dirs, rays, self._device, what), self._device)
         buffer = hits.buffer if isinstance(hits, RayHits) else hits
         n = int(buffer.shape[0])
         p = _ffi.BsdfQueryParams()
         p.count, p.mode = n, mode
-        if kind == "numpy":
-            if dirs.shape[1] == 3:
-                dirs = np.concatenate([dirs, np.zeros((n, 1), np.float32)], axis=1)
-            out = np.empty((n, 8), np.float32)
-            p.hits, p.dirs, p.out = buffer.ctypes.data, dirs.ctypes.data, out.ctypes.data
-            p.rays = rays.ctypes.data if rays is not None else None
-            self._check(self._lib.lrhip_query_bsdf(self._ctx, C.byref(p)))
-            return BsdfResults(out)
-        import torch
-        padded = dirs.shape[1] == 3
-        if padded:
-            dirs = torch.nn.functional.pad(dirs, (0, 1)).contiguous()
-        if sync or padded:  # (the padding copy runs on torch's stream, the query on the context's: the copy is waited for whatever `sync` says)
-            torch.cuda.current_stream(buffer.device).synchronize()
-        out = torch.empty((n, 8), dtype=torch.float32, device=buffer.device)
-        p.hits, p.dirs, p.out = buffer.data_ptr(), dirs.data_ptr(), out.data_ptr()
-        p.rays = rays.data_ptr() if rays is not None else None
-        p.flags = _ffi.RAY_DEVICE_POINTERS
-        self._check(self._lib.lrhip_query_bsdf(self._ctx, C.byref(p)))
-        if sync:
-            self.synchronize()
+        dirs, out = a.pad(dirs, 4), a.empty((n, 8))
+        p.hits, p.rays, p.dirs, p.out = a.ptr(buffer), a.ptr(rays), a.ptr(dirs), a.ptr(out)
+        self._call(self._lib.lrhip_query_bsdf, p, a, sync)
         return BsdfResults(out)
 
     def bsdf_evaluate(self, hits, wi, rays=None, sync: bool = True) -> BsdfResults:
@@ -885,36 +881,15 @@ class MegaPathRenderer:
         includes the selection probability; pdf = 0 marks a failed sample.  numpy arrays go through host pointers; torch tensors on this
         renderer's GPU are read in place (an [N, 3] array is padded by a copy) and the results stay on the device (synchronisation as in
         trace())."""
-        kind = check_light_args(hits, u, points, None, self._device, "sample")
-        records = points if points is not None else (hits.buffer if isinstance(hits, RayHits) else hits)
+        a = _Arrays(check_light_args(hits, u, points, None, self._device, "sample"), self._device)
+        records = a.pad(points, 4) if points is not None else (hits.buffer if isinstance(hits, RayHits) else hits)
         n = int(records.shape[0])
         p = _ffi.LightQueryParams()
         p.count, p.mode = n, _ffi.LIGHT_SAMPLE
         p.flags = _ffi.LIGHT_FROM_POINTS if points is not None else 0
-        if kind == "numpy":
-            pad = lambda a: np.concatenate([a, np.zeros((n, 1), np.float32)], axis=1) if a.shape[1] == 3 else a  # noqa: E731
-            u = pad(u)
-            if points is not None:
-                records = pad(records)
-            rays, out = np.empty((n, 8), np.float32), np.empty((n, 8), np.float32)
-            p.hits, p.dirs, p.out_rays, p.out = records.ctypes.data, u.ctypes.data, rays.ctypes.data, out.ctypes.data
-            self._check(self._lib.lrhip_query_light(self._ctx, C.byref(p)))
-            return LightSamples(rays, out)
-        import torch
-        padded = u.shape[1] == 3 or (points is not None and records.shape[1] == 3)
-        pad = lambda a: torch.nn.functional.pad(a, (0, 1)).contiguous() if a.shape[1] == 3 else a  # noqa: E731
-        u = pad(u)
-        if points is not None:
-            records = pad(records)
-        if sync or padded:  # (the padding copy runs on torch's stream, the query on the context's: the copy is waited for whatever `sync` says)
-            torch.cuda.current_stream(records.device).synchronize()
-        rays = torch.empty((n, 8), dtype=torch.float32, device=records.device)
-        out = torch.empty((n, 8), dtype=torch.float32, device=records.device)
-        p.hits, p.dirs, p.out_rays, p.out = records.data_ptr(), u.data_ptr(), rays.data_ptr(), out.data_ptr()
-        p.flags |= _ffi.RAY_DEVICE_POINTERS
-        self._check(self._lib.lrhip_query_light(self._ctx, C.byref(p)))
-        if sync:
-            self.synchronize()
+        u, rays, out = a.pad(u, 4), a.empty((n, 8)), a.empty((n, 8))
+        p.hits, p.dirs, p.out_rays, p.out = a.ptr(records), a.ptr(u), a.ptr(rays), a.ptr(out)
+        self._call(self._lib.lrhip_query_light, p, a, sync)
         return LightSamples(rays, out)
 
     def light_evaluate(self, hits, rays, sync: bool = True) -> LightResults:
@@ -922,25 +897,14 @@ class MegaPathRenderer:
         emitter gives its L towards the ray's origin and the pdf light_sample would have had for that point (kind _ffi.LIGHT_KIND_AREA), a miss
         the environment's (LIGHT_KIND_ENVIRONMENT), anything else L = 0, pdf = 0 (LIGHT_KIND_NONE): what a path tracer weighs a BSDF-sampled
         ray's emission with.  Otherwise as light_sample."""
-        kind = check_light_args(hits, None, None, rays, self._device, "evaluate")
+        a = _Arrays(check_light_args(hits, None, None, rays, self._device, "evaluate"), self._device)
         buffer = hits.buffer if isinstance(hits, RayHits) else hits
         n = int(buffer.shape[0])
         p = _ffi.LightQueryParams()
         p.count, p.mode = n, _ffi.LIGHT_EVALUATE
-        if kind == "numpy":
-            out = np.empty((n, 8), np.float32)
-            p.hits, p.rays, p.out = buffer.ctypes.data, rays.ctypes.data, out.ctypes.data
-            self._check(self._lib.lrhip_query_light(self._ctx, C.byref(p)))
-            return LightResults(out)
-        import torch
-        if sync:
-            torch.cuda.current_stream(buffer.device).synchronize()
-        out = torch.empty((n, 8), dtype=torch.float32, device=buffer.device)
-        p.hits, p.rays, p.out = buffer.data_ptr(), rays.data_ptr(), out.data_ptr()
-        p.flags = _ffi.RAY_DEVICE_POINTERS
-        self._check(self._lib.lrhip_query_light(self._ctx, C.byref(p)))
-        if sync:
-            self.synchronize()
+        out = a.empty((n, 8))
+        p.hits, p.rays, p.out = a.ptr(buffer), a.ptr(rays), a.ptr(out)
+        self._call(self._lib.lrhip_query_light, p, a, sync)
         return LightResults(out)
 
     def last_light_ms(self) -> float:
@@ -956,26 +920,13 @@ class MegaPathRenderer:
         p.flags = _ffi.SAMPLER_START if start else 0
         table = (C.c_uint32 * max(len(codes), 1))(*codes)
         p.pattern = C.cast(table, C.c_void_p)
-        if kind == "numpy":
-            out = np.empty((n, floats), np.float32)
-            p.state, p.out = state.ctypes.data, out.ctypes.data if floats else None
-            p.streams = streams.ctypes.data if streams is not None else None
-            p.indices = indices.ctypes.data if indices is not None else None
-            self._check(self._lib.lrhip_query_sampler(self._ctx, C.byref(p)))
-            return out
-        import torch
-        out = torch.empty((n, floats), dtype=torch.float32, device=state.device)
-        if n != 0 and (state.data_ptr() % 16 != 0 or (floats and out.data_ptr() % 16 != 0)):
+        a = _Arrays(kind, self._device)
+        out = a.empty((n, floats))
+        p.state, p.out = a.ptr(state), a.ptr(out) if floats else None
+        p.streams, p.indices = a.ptr(streams), a.ptr(indices)
+        if a.torch and n != 0 and (p.state % 16 != 0 or (floats and p.out % 16 != 0)):
             raise ValueError("sampler: the state must be 16-byte aligned on the device")
-        p.state, p.out = state.data_ptr(), out.data_ptr() if floats else None
-        p.streams = streams.data_ptr() if streams is not None else None
-        p.indices = indices.data_ptr() if indices is not None else None
-        p.flags |= _ffi.RAY_DEVICE_POINTERS
-        if sync:
-            torch.cuda.current_stream(state.device).synchronize()
-        self._check(self._lib.lrhip_query_sampler(self._ctx, C.byref(p)))
-        if sync:
-            self.synchronize()
+        self._call(self._lib.lrhip_query_sampler, p, a, sync)
         return out
 
     def sampler_start(self, streams=None, sample: int = 0, count: int | None = None, indices=None, on_device: bool = False, sync: bool = True):
@@ -1010,36 +961,17 @@ class MegaPathRenderer:
         u, pixels: what check_camera_args accepts.  Returns CameraRays: the rays, ready for trace(), the filter weight a path's throughput
         starts as, the film position and the pixel.  numpy arrays go through host pointers; torch tensors on this renderer's GPU are read in
         place and the results stay on the device (synchronisation as in trace())."""
-        kind = check_camera_args(u, pixels, self.width * self.height, self._device)
+        a = _Arrays(check_camera_args(u, pixels, self.width * self.height, self._device), self._device)
         n = int(u.shape[0])
-        padded = u.shape[1] == 2
-        if padded and self._scene is not None and int(self._scene.view().camera.kind) == 1:  # LR_CAMERA_THIN_LENS
+        if u.shape[1] == 2 and self._scene is not None and int(self._scene.view().camera.kind) == 1:  # LR_CAMERA_THIN_LENS
             raise ValueError("camera: a thin lens needs u = (u_filter, u_lens), [N, 4]")
         p = _ffi.CameraQueryParams()
         p.count = n
-        if kind == "numpy":
-            if padded:
-                u = np.concatenate([u, np.full((n, 2), 0.5, np.float32)], axis=1)
-            rays, out = np.empty((n, 8), np.float32), np.empty((n, 4), np.float32)
-            p.u, p.out_rays, p.out = u.ctypes.data, rays.ctypes.data, out.ctypes.data
-            p.pixels = pixels.ctypes.data if pixels is not None else None
-            self._check(self._lib.lrhip_query_camera(self._ctx, C.byref(p)))
-            return CameraRays(rays, out)
-        import torch
-        if padded:
-            u = torch.nn.functional.pad(u, (0, 2), value=0.5).contiguous()
-        if sync or padded:  # (the padding copy runs on torch's stream, the query on the context's: the copy is waited for whatever `sync` says)
-            torch.cuda.current_stream(u.device).synchronize()
-        rays = torch.empty((n, 8), dtype=torch.float32, device=u.device)
-        out = torch.empty((n, 4), dtype=torch.float32, device=u.device)
-        if n != 0 and u.data_ptr() % 16 != 0:
+        u, rays, out = a.pad(u, 4, 0.5), a.empty((n, 8)), a.empty((n, 4))
+        p.u, p.pixels, p.out_rays, p.out = a.ptr(u), a.ptr(pixels), a.ptr(rays), a.ptr(out)
+        if a.torch and n != 0 and p.u % 16 != 0:
             raise ValueError("camera: u must be 16-byte aligned on the device")
-        p.u, p.out_rays, p.out = u.data_ptr(), rays.data_ptr(), out.data_ptr()
-        p.pixels = pixels.data_ptr() if pixels is not None else None
-        p.flags = _ffi.RAY_DEVICE_POINTERS
-        self._check(self._lib.lrhip_query_camera(self._ctx, C.byref(p)))
-        if sync or padded:  # (the padded copy must outlive the kernel that reads it)
-            self.synchronize()
+        self._call(self._lib.lrhip_query_camera, p, a, sync)
         return CameraRays(rays, out)
 
     def camera_samples(self, sample: int, pixels=None, on_device: bool = False, sync: bool = True):
@@ -1060,31 +992,15 @@ class MegaPathRenderer:
         added to pixel pixels[k] (None: k) of the film the context accumulates into, in stream order with render() and download().  values,
         pixels: what check_splat_args accepts; the caller has multiplied the camera weight and the shutter weight in.  Distinct pixels in one
         call give a bit-determined film; several records of one pixel are added in no fixed order."""
-        kind = check_splat_args(values, pixels, clamp, self.width * self.height, self._device)
+        a = _Arrays(check_splat_args(values, pixels, clamp, self.width * self.height, self._device), self._device)
         n = int(values.shape[0])
-        padded = values.shape[1] == 3
         p = _ffi.FilmSplatParams()
         p.count, p.clamp = n, 0.0 if clamp is None else clamp
-        if kind == "numpy":
-            if padded:
-                values = np.concatenate([values, np.zeros((n, 1), np.float32)], axis=1)
-            p.values = values.ctypes.data
-            p.pixels = pixels.ctypes.data if pixels is not None else None
-            self._check(self._lib.lrhip_film_splat(self._ctx, C.byref(p)))
-            return
-        import torch
-        if padded:
-            values = torch.nn.functional.pad(values, (0, 1)).contiguous()
-        if sync or padded:
-            torch.cuda.current_stream(values.device).synchronize()
-        if n != 0 and values.data_ptr() % 16 != 0:
+        values = a.pad(values, 4)
+        p.values, p.pixels = a.ptr(values), a.ptr(pixels)
+        if a.torch and n != 0 and p.values % 16 != 0:
             raise ValueError("splat: values must be 16-byte aligned on the device")
-        p.values = values.data_ptr()
-        p.pixels = pixels.data_ptr() if pixels is not None else None
-        p.flags = _ffi.RAY_DEVICE_POINTERS
-        self._check(self._lib.lrhip_film_splat(self._ctx, C.byref(p)))
-        if sync or padded:  # (the padded copy must outlive the kernel that reads it)
-            self.synchronize()
+        self._call(self._lib.lrhip_film_splat, p, a, sync)
 
     def last_camera_ms(self) -> float:
         """lrhip_last_camera_ms: HIP-event time of the kernel(s) of the last sampler_start() / sampler_draw() / camera_rays() / film_splat()"""
@@ -1100,22 +1016,13 @@ class MegaPathRenderer:
         for a caller who has bound the context to torch's stream (set_stream).  The host Scene is not touched: a later upload() of it, with
         or without keep_film, brings the host's tables back; Scene.set_instance_transforms keeps it in step."""
         count = int(self._scene.view().instance_count) if self._scene is not None else None
-        kind = check_instance_transforms(matrices, instances, count, self._device)
+        a = _Arrays(check_instance_transforms(matrices, instances, count, self._device), self._device)
         p = _ffi.InstanceUpdateParams()
         p.count = int(matrices.shape[0])
-        if kind == "numpy":
-            ids = np.ascontiguousarray(instances, dtype=np.uint32) if instances is not None else None
-            p.object_to_world = matrices.ctypes.data
-            p.instances = ids.ctypes.data if ids is not None else None
-            self._check(self._lib.lrhip_set_instance_transforms(self._ctx, C.byref(p)))
-            return
-        import torch
-        p.object_to_world = matrices.data_ptr()
-        p.instances = instances.data_ptr() if instances is not None else None
-        p.flags = _ffi.RAY_DEVICE_POINTERS
-        if sync:
-            torch.cuda.current_stream(matrices.device).synchronize()
-        self._check(self._lib.lrhip_set_instance_transforms(self._ctx, C.byref(p)))
+        if not a.torch and instances is not None:
+            instances = np.ascontiguousarray(instances, dtype=np.uint32)
+        p.object_to_world, p.instances = a.ptr(matrices), a.ptr(instances)
+        self._call(self._lib.lrhip_set_instance_transforms, p, a, sync, wait_after=False)
 
     def last_instance_update_ms(self) -> float:
         """lrhip_last_instance_update_ms: HIP-event time of the kernels of the last set_instance_transforms()"""
@@ -1136,22 +1043,12 @@ class MegaPathRenderer:
         keep_film, brings the host's tables back; Scene.set_mesh_vertices keeps it in step."""
         if recompute_normals and normals is not None:
             raise ValueError("set_mesh_vertices: normals must be None with recompute_normals")
-        kind = check_mesh_vertices(positions, normals, mesh, first, None, self._device)  # mesh and range: the library checks them against the upload
+        a = _Arrays(check_mesh_vertices(positions, normals, mesh, first, None, self._device), self._device)  # mesh and range: the library's to check
         p = _ffi.MeshUpdateParams()
         p.mesh, p.first_vertex, p.count = int(mesh), int(first), int(positions.shape[0])
         p.flags = _ffi.MESH_RECOMPUTE_NORMALS if recompute_normals else 0
-        if kind == "numpy":
-            p.positions = positions.ctypes.data
-            p.normals = normals.ctypes.data if normals is not None else None
-            self._check(self._lib.lrhip_set_mesh_vertices(self._ctx, C.byref(p)))
-            return
-        import torch
-        p.positions = positions.data_ptr()
-        p.normals = normals.data_ptr() if normals is not None else None
-        p.flags |= _ffi.RAY_DEVICE_POINTERS
-        if sync:
-            torch.cuda.current_stream(positions.device).synchronize()
-        self._check(self._lib.lrhip_set_mesh_vertices(self._ctx, C.byref(p)))
+        p.positions, p.normals = a.ptr(positions), a.ptr(normals)
+        self._call(self._lib.lrhip_set_mesh_vertices, p, a, sync, wait_after=False)
 
     def last_mesh_update_ms(self) -> float:
         """lrhip_last_mesh_update_ms: HIP-event time of the kernels of the last set_mesh_vertices()"""

@@ -48,3 +48,16 @@ def test_default_builder_beats_the_round1b_builder_on_a_room(tmp_path):
         assert r.returncode == 0, r.stderr
         steps[name] = float(re.search(r"total steps/ray ([\d.]+)", r.stdout).group(1))
     assert steps["default"] < 0.92 * steps["round1b"], steps
+
+
+def test_query_column_arithmetic_under_the_sanitizers(tmp_path):
+    """tools/query_columns_check.cpp: the staged-call routine's column arithmetic (csrc/hip/query_columns.h: which bytes of which host
+    column are chunk i, what a slot must hold) as a stand-alone program under AddressSanitizer and UBSan, for 0, 1, 2^20, 2^20 + 65 and
+    2^31 - 1 records"""
+    if shutil.which("g++") is None:
+        pytest.skip("no C++ compiler")
+    exe = tmp_path / "query_columns_check"
+    subprocess.check_call(["g++", "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(_ffi.REPO_ROOT, "tools", "query_columns_check.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "query columns: ok" in r.stdout, r.stdout + r.stderr
