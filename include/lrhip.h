@@ -173,10 +173,14 @@ double lrhip_last_denoise_ms(lrhip_ctx *ctx);
  * trace_any are only reachable from inside a kernel, src/base/geometry.cpp:218-279).  Camera, integrator and sampler play no part;
  * LRHIP_ERROR_INVALID before any scene has been uploaded.
  *   What can be hit   the baked BVH triangles of VISIBLE instances (lr_instance.visible, baked flag bit 0), exactly as in the renderer.
- *   A hit             has t_min < t < t_max, both strict; t_max = +inf is allowed.  Directions need not be normalised: t is in units of
- *                     |d|.  u, v: the weights of the triangle's second and third vertex; inst, prim: the instance and primitive ids of
- *                     the renderer's hit record (lr_scene.instances, the primitive within its mesh); tri indexes lr_scene.accel.triangles;
- *                     reserved is written 0.
+ *   A hit             has max(t_min, +0) < t < t_max, both strict; t_max = +inf is allowed.  The search never reaches behind the origin:
+ *                     t_min = -0.0 or a negative t_min searches from +0, and a ray whose t_max is not above +0 finds nothing.
+ *                     Directions need not be normalised: t, t_min and t_max are in units of |d|, for every finite non-zero d, denormal
+ *                     components and lengths up to 2^126 included (a direction whose squared length is within 4e-7 of 1 is traced bit for
+ *                     bit as given; any other is normalised first and t scaled back).  A hit whose t does not fit float32 in the caller's
+ *                     units reports t = +inf (or a denormal) with valid ids: inst tells a hit from a miss.  u, v: the weights of the
+ *                     triangle's second and third vertex; inst, prim: the instance and primitive ids of the renderer's hit record
+ *                     (lr_scene.instances, the primitive within its mesh); tri indexes lr_scene.accel.triangles; reserved is written 0.
  *   A miss            t = +inf, u = v = 0, inst = prim = tri = LR_INVALID_ID.
  *   LRHIP_RAY_ANY     stops at the first accepted triangle: out[i] = 1 (occluded) or 0.
  *   Screened rays     a ray with a non-finite component (t_max = +inf is the one exception), a zero direction, or for which

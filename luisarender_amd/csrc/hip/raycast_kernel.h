@@ -5,7 +5,7 @@
 // wave-level grab: one atomic per wave for all its idle lanes -- and for its next few refills, RaycastArgs::grab rays at a time: every
 // wave of the device adds to the same word, and at one atomic per 64 rays that word's throughput was what bounded the first form of
 // this kernel.  The lane loads its 32-byte ray as two dwordx4 and -- unless the ray is screened out below -- calls
-// trav_begin; the wave traces with has_next = false; a lane whose ray ended stores its 32-byte record (closest hit) or its occlusion
+// trav_begin with the ray in the loop's units (raycast_ray below); the wave traces with has_next = false; a lane whose ray ended stores its 32-byte record (closest hit) or its occlusion
 // word (any hit) and is idle again.  A lane's walk does not depend on its neighbours, so a ray's result is a function
 // of the ray and the scene only: bit-identical from run to run and wherever the ray stands in the batch.
 //
@@ -19,6 +19,9 @@
 
 #ifndef LR_RAYCAST_REFILL
 #define LR_RAYCAST_REFILL 16
+#endif
+#ifndef LR_RAYCAST_CALLER_UNITS
+#define LR_RAYCAST_CALLER_UNITS 1// 0: the ray goes to the loop as the caller gave it -- right for unit directions and t_min > 0 only; the baseline of raycast_ray's A/B
 #endif
 #ifndef LR_RAYCAST_WAVES
 #define LR_RAYCAST_WAVES 4// waves per SIMD asked of the register allocator: what the LDS of a block (stack + staging area) allows anyway
@@ -48,6 +51,48 @@ LR_D bool raycast_ray_valid(const float4 &a, const float4 &b) {
     return finite && moves && b.w > a.w;// (both finite or t_max = +inf here: an ordinary compare)
 }
 
+// THE CALLER'S UNITS (lrhip.h: "directions need not be normalised: t is in units of |d|", "the search starts at max(t_min, +0)").  The traversal
+// loop is the renderers', whose rays have unit directions and t_min >= 0, and it relies on both: safe_inverse caps |1 / d| at 1e30 per component,
+// so the slab tests of a direction shorter than 2^-100 walk along (+-1, +-1, +-1) while the triangle test uses d; the triangle test's products
+// underflow or overflow with |d|; and a child whose entry distance max(planes, t_min) is negative or -0.0 has a key with the sign bit set, which
+// is how the loop marks a child it missed.  So the prologue hands the loop what it was built for, by the rule of the radiance queries
+// (megapath_kernel.h, the kFeatQuery prologue) and surface_unit_direction:
+//   * t_min = max(t_min, +0) (a select, so that -0.0 becomes +0 whatever v_max makes of signed zeros);
+//   * a direction whose squared length is within 4e-7 of 1 is taken bit for bit -- a normalised ray's result has the bits it always had;
+//   * any other finite non-zero d: a power of two first brings its largest component into 2^-60 .. 2^60 (exact; neither the squares nor v_sqrt_f32
+//     and v_rcp_f32, 1 ulp each on normal numbers, meet a denormal or overflow), d becomes dp * (1 / len), and the interval's ends take |d| in two
+//     factors, len and 2^-k, so that no product is 0 x inf (raycast_scale: in the order that keeps the intermediate in range);
+//   * a hit's t goes back to the caller's units at the store, by the factors 1 / len and 2^k: it overflows to +inf or underflows only where the
+//     caller's units make it (inst tells a hit from a miss).
+// tests/raycast_judge.py derives its error bands from exactly these operations.
+struct RaycastUnits {
+    float inv_len, pre;// t of the caller = raycast_scale(t of the loop, inv_len, pre); 1, 1 for a direction taken bit for bit
+};
+// t * f * 2^k, k in (-100, 0, 100) and f within 2^-61 .. 2^61: the power of two goes first where it brings t TOWARDS 1 (|t| >= 1 and k < 0, |t| < 1
+// and k > 0) and last otherwise, so that the intermediate leaves float32's range only if the result does.  (t * f) * 2^k alone turns t_max = 2^70
+// under |d| = 2^-41 into +inf, where the product is 2^29.  The power of two is exact: one rounding either way.
+LR_D float raycast_scale(float t, float f, float pow2) {
+    return ((fabsf(t) >= 1.f) == (pow2 < 1.f)) ? (t * pow2) * f : (t * f) * pow2;
+}
+LR_D Ray raycast_ray(const float4 &a, const float4 &b, RaycastUnits &units) {
+    auto d = mk3(b.x, b.y, b.z);
+    units.inv_len = 1.f, units.pre = 1.f;
+    if (!LR_RAYCAST_CALLER_UNITS) { return Ray{mk3(a.x, a.y, a.z), a.w, d, b.w}; }
+    auto t_min = a.w > 0.f ? a.w : 0.f, t_max = b.w;
+    if (!(fabsf(dot(d, d) - 1.f) <= 4e-7f)) {
+        const auto m = fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
+        const auto pre = m < 0x1p-40f ? 0x1p100f : (m > 0x1p40f ? 0x1p-100f : 1.f);
+        const auto unpre = m < 0x1p-40f ? 0x1p-100f : (m > 0x1p40f ? 0x1p100f : 1.f);
+        const auto dp = d * pre;
+        const auto len = __builtin_amdgcn_sqrtf(dot(dp, dp));
+        const auto inv_len = __builtin_amdgcn_rcpf(len);
+        d = dp * inv_len;
+        t_min = raycast_scale(t_min, len, unpre), t_max = raycast_scale(t_max, len, unpre);
+        units.inv_len = inv_len, units.pre = pre;
+    }
+    return Ray{mk3(a.x, a.y, a.z), t_min, d, t_max};
+}
+
 template<bool ALPHA>
 __global__ __launch_bounds__(kBlockThreads, LR_RAYCAST_WAVES) void raycast_kernel(DScenePtr scene_ptr, RaycastArgs args) {
     const DScene &scene = *(const DScene *)scene_ptr;
@@ -60,26 +105,27 @@ __global__ __launch_bounds__(kBlockThreads, LR_RAYCAST_WAVES) void raycast_kerne
     const auto shadow = args.phase == kPhaseShadow;
     const auto hits = static_cast<float4 *>(args.out);
     const auto words = static_cast<uint32_t *>(args.out);
-    const auto store = [&](uint32_t k, const TravState &tr) {
+    const auto store = [&](uint32_t k, const TravState &tr, const RaycastUnits &units) {
         if (shadow) {
             words[k] = tr.occluded ? 1u : 0u;
         } else {
             const auto hit = tr.hit.inst != kInvalid;
             const auto record = hits + static_cast<size_t>(k) * 2u;
-            record[0] = make_float4(hit ? tr.t_max : __uint_as_float(0x7f800000u), tr.hit.u, tr.hit.v, __uint_as_float(tr.hit.inst));
+            record[0] = make_float4(hit ? raycast_scale(tr.t_max, units.inv_len, units.pre) : __uint_as_float(0x7f800000u), tr.hit.u, tr.hit.v, __uint_as_float(tr.hit.inst));
             record[1] = make_float4(__uint_as_float(tr.hit.prim), __uint_as_float(tr.hit.tri), 0.f, 0.f);
         }
     };
     TravState tr{};
     tr.phase = kPhaseIdle;
     auto index = kInvalid; // the ray this lane traces
+    RaycastUnits units{1.f, 1.f};// ... and what takes its t back to the caller's units
     auto w_next = 0u, w_end = 0u;// wave-uniform: the rays [w_next, w_end) are this wave's to hand to its lanes
     auto exhausted = false;      // wave-uniform: the counter has passed the last ray
     const Ray none{};
     for (;;) {
         // ---- lanes whose ray ended: store the result
         if (tr.phase == kPhaseIdle && index != kInvalid) {
-            store(index, tr);
+            store(index, tr, units);
             index = kInvalid;
         }
         // ---- idle lanes take the next rays of the wave's own range; an empty range is refilled with ONE atomic for the whole wave
@@ -105,9 +151,9 @@ __global__ __launch_bounds__(kBlockThreads, LR_RAYCAST_WAVES) void raycast_kerne
                 tr.occluded = false;
                 if (raycast_ray_valid(a, b)) {
                     index = k;
-                    trav_begin(tr, Ray{mk3(a.x, a.y, a.z), a.w, mk3(b.x, b.y, b.z), b.w}, args.phase);
+                    trav_begin(tr, raycast_ray(a, b, units), args.phase);
                 } else {
-                    store(k, tr);// screened: a miss, and the lane stays idle
+                    store(k, tr, units);// screened: a miss, and the lane stays idle
                 }
             }
         }

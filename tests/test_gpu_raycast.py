@@ -131,6 +131,44 @@ def test_screened_rays(renderer):
     assert _is_miss(renderer.trace(np.ascontiguousarray(batch[rows]))).all()
 
 
+def test_direction_length_and_negative_t_min_beside_their_neighbours(renderer):
+    """what the header promises of the caller's units, among ordinary rays: a direction scaled by a power of two finds the same triangle with t scaled
+    the other way and the same u, v, to within the bars of the reference comparison (the normalisation rounds); directions of 2^-140, whose components
+    are denormal and rounded, are judged in test_gpu_raycast_edges.py; t_min =
+    -0.0 or negative searches from +0 -- the result of t_min = +0; and the neighbours keep their bits"""
+    scene, rays, _ = R.case("soup")
+    renderer.upload(scene)
+    batch = rays[:200].copy()
+    batch[:, 3] = 0.0
+    clean = renderer.trace(batch)
+    clean_bits = clean.buffer.view(np.uint32).copy()
+    clean_any = renderer.trace(batch, any_hit=True)
+    hit_rows = np.nonzero(np.asarray(clean.hit))[0]
+    assert len(hit_rows) >= 40
+    scaled = {int(row): k for row, k in zip(hit_rows[0:16], (-120, -100, -30, -10, 10, 30, 100, 126) * 2)}
+    negative = {int(row): value for row, value in zip(hit_rows[16:24], (-0.0, -1.0, -1e30, -1e-40) * 2)}
+    changed = batch.copy()
+    for row, k in scaled.items():
+        changed[row, 4:7] = (batch[row, 4:7].astype(np.float64) * 2.0 ** k).astype(np.float32)
+        assert (changed[row, 4:7].astype(np.float64) == batch[row, 4:7].astype(np.float64) * 2.0 ** k).all()  # exact: no component turns denormal
+    for row, value in negative.items():
+        changed[row, 3] = value
+    hits = renderer.trace(changed)
+    occluded = renderer.trace(changed, any_hit=True)
+    others = np.setdiff1d(np.arange(len(batch)), list(scaled) + list(negative))
+    assert np.array_equal(hits.buffer.view(np.uint32)[others], clean_bits[others]) and np.array_equal(occluded[others], clean_any[others])
+    rows = np.array(sorted(negative))
+    assert np.array_equal(hits.buffer.view(np.uint32)[rows], clean_bits[rows]) and occluded[rows].all()  # the bits of t_min = +0
+    for row, k in scaled.items():
+        assert occluded[row] and hits.tri[row] == clean.tri[row] and hits.inst[row] == clean.inst[row] and hits.prim[row] == clean.prim[row], (row, k)
+        want = float(clean.t[row]) * 2.0 ** -k
+        if want > np.finfo(np.float32).max:
+            assert np.isposinf(hits.t[row]), (row, k)
+        else:
+            assert abs(float(hits.t[row]) - want) <= max(R.BAR_T * want, 2.0 ** -149), (row, k)
+        assert abs(hits.u[row] - clean.u[row]) <= R.BAR_UV and abs(hits.v[row] - clean.v[row]) <= R.BAR_UV, (row, k)
+
+
 QUADS = """
 Texture holes : Checkerboard { on : Constant { v { 1 } } off : Constant { v { 0 } } scale { 1 } }
 Surface cutout : Matte { Kd : Constant { v { 0.7 } } alpha { @holes } }
