@@ -90,7 +90,9 @@ VPT_HIPFLAGS ?= --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -ffp-contract=o
 CALL_SAFE_FLAGS ?= -mllvm -amdgpu-spill-sgpr-to-vgpr=0
 # (the choice follows the kFeatVpt bit, 256, by design: whatever mask instantiates the volumetric kernel -- megapath_variant.hip tests the
 # same bit -- takes its arithmetic; today these are 256-259)
-variant_flags = $(if $(filter-out 0,$(shell echo $$(( $(1) & 256 )))),$(VPT_HIPFLAGS),$(HIPFLAGS)) $(CALL_SAFE_FLAGS)
+# The gather kernels (kFeatGather, 131072: lrhip_gather_irradiance) take that arithmetic too: one of their samples is held to the plan query's
+# answer continued by the caller (tests/test_gpu_gather.py), and lrhip_gather.o, which holds the plan kernel, is built with it
+variant_flags = $(if $(filter-out 0,$(shell echo $$(( $(1) & (256 | 131072) )))),$(VPT_HIPFLAGS),$(HIPFLAGS)) $(CALL_SAFE_FLAGS)
 $(OBJDIR)/variant_%.o: $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(call variant_flags,$*) -DLR_VARIANT=$* -c -o $@ $(HIPDIR)/megapath_variant.hip
@@ -128,6 +130,12 @@ lrhip_light_FLAGS = $(lrhip_bsdf_FLAGS)
 # flag; they are built with the oracle's arithmetic because a query hands ONE number, ray or weight to its caller: the Sobol sampler's pixel draw has
 # a multiply-subtract that contraction would fuse, the camera's normalize a division and the filter's weight another
 lrhip_camera_FLAGS = -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-approx-func
+# lrhip_lightmap.o holds the kernels of the UV rasteriser (csrc/hip/lightmap_kernels.h).  They decide coverage in float64 and are held, texel by texel,
+# to a float64 numpy rasteriser (tests/gather_reference.py): no fp contraction, and none of -fapprox-func's marks on the divisions
+lrhip_lightmap_FLAGS = $(lrhip_camera_FLAGS)
+# lrhip_gather.o holds the kernels of the gather vertex query (csrc/hip/gather_kernel.h): the light sample and the white Lambert closure of a path that
+# starts at a surface point.  It makes lrhip_light.o's real calls and its answers are held to the light and BSDF queries' bits, so it is built as they are
+lrhip_gather_FLAGS = $(lrhip_bsdf_FLAGS)
 $(HIP_OBJ): $(OBJDIR)/%.o: $(HIPDIR)/%.hip $(HIP_HDR) Makefile
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $($*_FLAGS) -c -o $@ $<

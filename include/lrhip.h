@@ -656,6 +656,108 @@ int lrhip_set_mesh_vertices(lrhip_ctx *ctx, const lrhip_mesh_update_params *para
 /* HIP-event time of the kernels of the last lrhip_set_mesh_vertices call, in ms; synchronises */
 double lrhip_last_mesh_update_ms(lrhip_ctx *ctx);
 
+/* Lightmap texels (no reference equivalent): the UV rasteriser of a bake.  Which point of ONE instance's mesh each texel of a
+ * width x height lightmap over the mesh's UV chart stands for, as the record the surface, BSDF and light queries take for "a texel's point
+ * without a ray": out[j * width + i] = lrhip_ray_hit { t = 0, u, v, inst = instance, prim, tri = 0xffffffff, reserved = { flags, 0 } }.
+ *   Texels            texel (i, j) has its centre at uv = ((i + 1/2) / width, (j + 1/2) / height); row 0 is at v = 0.  Nothing wraps: a chart
+ *                     outside [0, 1]^2 is not covered there.
+ *   Coverage          a texel is CENTRE-COVERED by a triangle when the three edge functions of the triangle's UVs at its centre are >= 0, with
+ *                     the orientation normalised (a mirrored chart works as well); a triangle without area in UV space, with a non-finite UV
+ *                     or with a vertex index outside its mesh owns nothing.  With LRHIP_LIGHTMAP_CONSERVATIVE a texel is also TOUCHED by a
+ *                     triangle when the texel's closed square meets it.  Centre coverage beats touching, and the lowest prim wins within each
+ *                     class: overlapping charts are the caller's business, and the result is a function of the chart alone, bit-identical
+ *                     from run to run.  All decisions are made in float64 from the fp32 UVs of the device vertex table.
+ *   u, v              the barycentrics of the centre in the owner triangle, p = (1 - u - v) p0 + u p1 + v p2; for a touched texel those of the
+ *                     triangle's point nearest to the centre (UV distance).  Rounded to fp32 last and kept at u, v >= 0, u + v <= 1.
+ *   flags             reserved[0]: LRHIP_LIGHTMAP_TEXEL_CENTRE or LRHIP_LIGHTMAP_TEXEL_TOUCHED.  A texel nobody owns gets the miss record
+ *                     inst = prim = tri = 0xffffffff with flags 0, which every query answers with its invalid record.
+ *   What it reads     the instance's mesh in the device's vertex and triangle tables, as lrhip_update_scene and lrhip_set_mesh_vertices left
+ *                     them; positions do not matter, only u v and the indices.  The instance's mesh and property flags come from
+ *                     the host's copy of its handle as the uploads wrote it: nothing is read back.
+ *   Pointers          out: width * height records.  With LRHIP_RAY_DEVICE_POINTERS device memory, 16-byte aligned (else LRHIP_ERROR_INVALID),
+ *                     written asynchronously on the context's stream; without it host memory, staged 2^20 records at a time, and the call
+ *                     synchronises.
+ *   Errors            LRHIP_ERROR_INVALID before any upload, for an instance out of range, NULL out with width * height > 0, unknown flags and
+ *                     width * height > LRHIP_RAY_MAX_COUNT; LRHIP_ERROR_UNSUPPORTED for an instance whose mesh has no vertex UVs
+ *                     (LR_SHAPE_HAS_VERTEX_UV).  width or height 0 is legal and launches nothing.
+ *   Not done          unwrapping, seam dilation, filtered or supersampled texels, several instances in one map.                               */
+#define LRHIP_LIGHTMAP_CONSERVATIVE 256u
+#define LRHIP_LIGHTMAP_TEXEL_CENTRE 1u
+#define LRHIP_LIGHTMAP_TEXEL_TOUCHED 2u
+int lrhip_lightmap_texels(lrhip_ctx *ctx, uint32_t instance, uint32_t width, uint32_t height, uint32_t flags, void *out);
+/* HIP-event time of the kernels of the last lrhip_lightmap_texels call (a host-pointer call: summed over its chunks), in ms; synchronises */
+double lrhip_last_lightmap_ms(lrhip_ctx *ctx);
+
+/* The gather vertex: the plan of ONE irradiance sample at points the caller names -- a path that starts AT a surface point
+ * instead of along a camera ray.  For each record, MegaPath's shading vertex for a virtual white Lambert surface at the point (a Matte closure
+ * with Kd = 1, sigma = 0 on the record's shading frame, seen from its front): one light sample and one cosine-distributed continuation
+ * direction, with the throughput started at pi so that the path's radiance IS the irradiance sample, E = pi L_o.  The caller continues it:
+ *     sample = (shadow ray unoccluded ? nee : 0) + beta x (what `ray` finds, each emitter or environment weighted by balance(pdf, its light pdf))
+ * with lrhip_trace_rays, lrhip_query_light in evaluate mode and, for deeper paths, the other queries or lrhip_trace_radiance.
+ *   Records           lrhip_ray_hit[count], everything the surface, BSDF and light queries take: a hit of lrhip_trace_rays or a texel's
+ *                     (inst, prim, u, v) with tri = 0xffffffff (lrhip_lightmap_texels).  With LRHIP_GATHER_FROM_POINTS float[4][count] bare
+ *                     positions and, in `normals`, float[4][count] normals of any length but 0 (ng = ns = normalize(n)); both rays then start
+ *                     at the point itself, as lrhip_query_light's bare points do.
+ *   Random numbers    stream `streams[k]` (NULL: k) at sample index `sample_index`, exactly as lrhip_trace_radiance starts it: stream j is pixel
+ *                     (j mod W, (j div W) mod H)'s, the pixel draw and, for a thin lens, the lens draw are drawn and discarded, then the
+ *                     vertex's draws follow in MegaPath's order: light selection, light surface (2), lobe (not used), direction (2).  A map
+ *                     with more texels than the camera has pixels repeats streams: pass `streams` to decorrelate.
+ *   Result            lrhip_gather_vertex: ray = (robust origin, wi, 0, FLT_MAX) and pdf, the cosine density of wi; shadow, nee and light_pdf
+ *                     of the light sample (light_pdf = 0: it failed, nee = 0, the shadow ray may be non-finite); beta = pi f / pdf.  The
+ *                     point's own emission is not part of it.  The invalid record -- a non-finite u, v, point or normal, a zero normal, ids
+ *                     out of range, a miss -- is all zeros, and so is every record of a scene with neither lights nor an environment.
+ *   Scope, pointers   MegaPath scenes (else LRHIP_ERROR_UNSUPPORTED); pointers, alignment and errors as for lrhip_query_light.               */
+typedef struct lrhip_gather_vertex {
+    lrhip_ray ray;            /* the continuation ray */
+    lrhip_ray shadow;         /* the light sample's shadow ray */
+    float nee[3], light_pdf;
+    float beta[3], pdf;
+} lrhip_gather_vertex;        /* 96 bytes */
+typedef struct lrhip_gather_vertex_params {
+    const void *records;      /* lrhip_ray_hit[count]; LRHIP_GATHER_FROM_POINTS: float[4][count] = (p, -) */
+    const void *normals;      /* LRHIP_GATHER_FROM_POINTS: float[4][count] = (n, -); else not read */
+    const uint32_t *streams;  /* uint32_t[count] or NULL (stream k) */
+    void *out;                /* lrhip_gather_vertex[count] */
+    uint64_t count;           /* 0 is legal and launches nothing; at most LRHIP_RAY_MAX_COUNT */
+    uint32_t sample_index;
+    uint32_t flags;           /* LRHIP_RAY_DEVICE_POINTERS, LRHIP_GATHER_FROM_POINTS */
+} lrhip_gather_vertex_params;
+#define LRHIP_GATHER_FROM_POINTS 64u
+int lrhip_query_gather_vertex(lrhip_ctx *ctx, const lrhip_gather_vertex_params *params);
+
+/* Irradiance gathers: the hemisphere integral at points the caller names, on the device -- the second end of a lightmap or
+ * probe bake.  For every record, samples [spp_begin, spp_end) of MegaPath's estimator for paths that START at the record's point with the
+ * gather vertex above (next-event estimation at the point itself, MIS for what the continuation ray finds, then the scene's own path
+ * tracing to its max_depth with its Russian roulette), summed into out[k] = (sum E_r, sum E_g, sum E_b, n): the irradiance is sum / n.
+ * The kernels are the radiance query's (lrhip_trace_radiance) with another prologue, so everything of that call holds here:
+ *   Records, streams  as lrhip_query_gather_vertex: lrhip_ray_hit records (hits or texels), or with LRHIP_GATHER_FROM_POINTS positions and
+ *                     normals; stream streams[k] (NULL: k) is pixel (j mod W, (j div W) mod H)'s, so a map with more texels than the camera
+ *                     has pixels repeats streams -- correlated noise, an unbiased mean; pass `streams` to decorrelate.
+ *   Samples           the texel is the path's camera end: the continuation ray has depth 0.  A scene with max_depth 0 starts no ray: every
+ *                     valid record counts its samples with E = 0.  The point's own emission is not part of E.  Each sample goes through the
+ *                     film's accumulate rule (NaN / Inf rejected, clamp -- 0: the scene's film clamp) before it is summed.
+ *   Invalid records   (as lrhip_query_gather_vertex) give no sample: n stays 0.  A scene with neither lights nor an environment launches
+ *                     nothing and returns the sums of no sample, as lrhip_trace_radiance does; so does spp_begin >= spp_end.
+ *   LRHIP_GATHER_ACCUMULATE   out holds earlier sums and is added to (refinement); without it out is cleared first.
+ *   Determinism, pointers, scope, errors   as lrhip_trace_radiance: with one sample per call a record's result is a function of (record,
+ *                     stream, sample index) alone, wherever it stands in the batch; device pointers 16-byte aligned (streams 4-byte).          */
+typedef struct lrhip_gather_params {
+    const void *records;      /* lrhip_ray_hit[count]; LRHIP_GATHER_FROM_POINTS: float[4][count] = (p, -) */
+    const void *normals;      /* LRHIP_GATHER_FROM_POINTS: float[4][count] = (n, -); else not read */
+    const uint32_t *streams;  /* uint32_t[count] or NULL (stream k) */
+    void *out;                /* float[4][count]: (sum E_r, sum E_g, sum E_b, n) */
+    uint64_t count;           /* 0 is legal and launches nothing; at most LRHIP_RAY_MAX_COUNT */
+    uint32_t spp_begin, spp_end;
+    uint32_t flags;           /* LRHIP_RAY_DEVICE_POINTERS, LRHIP_GATHER_ACCUMULATE, LRHIP_GATHER_FROM_POINTS */
+    float clamp;              /* 0 = the scene's film clamp */
+} lrhip_gather_params;
+#define LRHIP_GATHER_ACCUMULATE 4u
+#define LRHIP_FEAT_GATHER 131072u /* the gather kernels (with LRHIP_FEAT_QUERY; never reported by lrhip_last_variant) */
+int lrhip_gather_irradiance(lrhip_ctx *ctx, const lrhip_gather_params *params);
+/* HIP-event time of the kernel(s) of the last lrhip_gather_irradiance or lrhip_query_gather_vertex call (a host-pointer call: summed over its
+ * chunks), in ms; synchronises */
+double lrhip_last_gather_ms(lrhip_ctx *ctx);
+
 /* The path's only collective: sum-reduce of the per-rank films to rank `root` over RCCL / xGMI, in place on the film
  * this context accumulates into, in stream order behind the renders.  `nccl_comm` is the caller's ncclComm_t (one per process /
  * GPU, created by the caller: ncclCommInitRank); librccl.so is loaded on first use, so the library has no link-time dependency

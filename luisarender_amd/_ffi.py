@@ -191,6 +191,23 @@ class LightQueryParams(C.Structure):
                 ("mode", u32), ("flags", u32)]
 
 
+class GatherVertex(C.Structure):
+    """lrhip_gather_vertex (include/lrhip.h): one row of the [N, 24] float32 buffer behind GatherVertices"""
+    _fields_ = [("ray", Ray), ("shadow", Ray), ("nee", f32 * 3), ("light_pdf", f32), ("beta", f32 * 3), ("pdf", f32)]
+
+
+class GatherVertexParams(C.Structure):
+    """lrhip_gather_vertex_params (include/lrhip.h)"""
+    _fields_ = [("records", C.c_void_p), ("normals", C.c_void_p), ("streams", C.c_void_p), ("out", C.c_void_p), ("count", u64),
+                ("sample_index", u32), ("flags", u32)]
+
+
+class GatherParams(C.Structure):
+    """lrhip_gather_params (include/lrhip.h)"""
+    _fields_ = [("records", C.c_void_p), ("normals", C.c_void_p), ("streams", C.c_void_p), ("out", C.c_void_p), ("count", u64),
+                ("spp_begin", u32), ("spp_end", u32), ("flags", u32), ("clamp", f32)]
+
+
 class SamplerQueryParams(C.Structure):
     """lrhip_sampler_query_params (include/lrhip.h)"""
     _fields_ = [("state", C.c_void_p), ("streams", C.c_void_p), ("indices", C.c_void_p), ("pattern", C.c_void_p), ("out", C.c_void_p),
@@ -246,10 +263,17 @@ LIGHT_KIND_AREA, LIGHT_KIND_ENVIRONMENT, LIGHT_KIND_NONE = 0, 1, 2
 DRAW_1D, DRAW_2D, DRAW_PIXEL_2D = 0, 1, 2
 SAMPLER_MAX_DRAWS = 64
 SAMPLER_START = 128
+GATHER_FROM_POINTS = 64  # LRHIP_GATHER_FROM_POINTS
+GATHER_ACCUMULATE = 4  # LRHIP_GATHER_ACCUMULATE
+FEAT_GATHER = 131072  # LRHIP_FEAT_GATHER
+LIGHTMAP_CONSERVATIVE = 256  # LRHIP_LIGHTMAP_CONSERVATIVE
+# word 6 of a texel record of lrhip_lightmap_texels: LRHIP_LIGHTMAP_TEXEL_CENTRE / TOUCHED
+LIGHTMAP_TEXEL_CENTRE, LIGHTMAP_TEXEL_TOUCHED = 1, 2
 
 STRUCTS = {"lrhip_surface_point": SurfacePoint, "lrhip_surface_query_params": SurfaceQueryParams,
 "lrhip_bsdf_result": BsdfResult, "lrhip_bsdf_query_params": BsdfQueryParams,
 "lrhip_light_result": LightResult, "lrhip_light_query_params": LightQueryParams,
+"lrhip_gather_vertex": GatherVertex, "lrhip_gather_vertex_params": GatherVertexParams, "lrhip_gather_params": GatherParams,
 "lrhip_sampler_query_params": SamplerQueryParams, "lrhip_camera_sample": CameraSample, "lrhip_camera_query_params": CameraQueryParams,
 "lrhip_film_splat_params": FilmSplatParams,
 "lrhip_denoise_params": DenoiseParams, "lrhip_ray": Ray, "lrhip_ray_hit": RayHit, "lrhip_ray_query_params": RayQueryParams,
@@ -392,6 +416,13 @@ def hip_lib(path: str | None = None) -> C.CDLL:
         lib.lrhip_set_mesh_vertices.argtypes = [C.c_void_p, C.POINTER(MeshUpdateParams)]
         lib.lrhip_last_mesh_update_ms.restype = C.c_double
         lib.lrhip_last_mesh_update_ms.argtypes = [C.c_void_p]
+        lib.lrhip_query_gather_vertex.argtypes = [C.c_void_p, C.POINTER(GatherVertexParams)]
+        lib.lrhip_gather_irradiance.argtypes = [C.c_void_p, C.POINTER(GatherParams)]
+        lib.lrhip_last_gather_ms.restype = C.c_double
+        lib.lrhip_last_gather_ms.argtypes = [C.c_void_p]
+        lib.lrhip_lightmap_texels.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.lrhip_last_lightmap_ms.restype = C.c_double
+        lib.lrhip_last_lightmap_ms.argtypes = [C.c_void_p]
         lib.lrhip_read_scene_table.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
         lib.lrhip_scene_table_bytes.restype = C.c_uint64
         lib.lrhip_scene_table_bytes.argtypes = [C.c_void_p, C.c_uint32]

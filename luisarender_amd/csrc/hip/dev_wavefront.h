@@ -37,6 +37,10 @@ enum : uint32_t {
     // consecutive caller-supplied rays instead of an 8x8 tile -- the path starts from the caller's ray instead of the camera's, its sums go
     // to the ray's record instead of the film
     kFeatQuery = 65536u,
+    // irradiance gathers (lrhip.h: lrhip_gather_irradiance), on top of kFeatQuery only: the query kernel whose work items are 64
+    // consecutive hit / texel records (or bare points with normals) instead of rays -- the path starts AT the record's point with the gather
+    // vertex of gather_vertex.h instead of along a ray; everything behind the prologue is the query kernel's
+    kFeatGather = 131072u,
     kFeatSceneMask = kFeatEnv | kFeatAlpha | kFeatDisney | kFeatMix | kFeatLayered
 };
 

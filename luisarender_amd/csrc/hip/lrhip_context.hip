@@ -29,7 +29,7 @@ void release_scene(lrhip_ctx *ctx) {
     ctx->scene_ready = false;
     ctx->nodes32 = nullptr, ctx->level_nodes = nullptr, ctx->level_offsets.clear();
     for (auto &b : ctx->mesh_adjacency) { b.release(); }
-    ctx->mesh_adjacency.clear(), ctx->meshes.clear(), ctx->mesh_light.clear();
+    ctx->mesh_adjacency.clear(), ctx->meshes.clear(), ctx->mesh_light.clear(), ctx->instance_handles.clear();
     ctx->surface_meshes_ready = false;
     // the queues of wavefront mode and the pool kernels' state records are sized for the scene (and the memory free at the time): a new
     // scene starts without them (76-89 GB kept until lrhip_destroy starved later allocations on the same GPU)
@@ -123,10 +123,10 @@ void lrhip_destroy(lrhip_ctx *ctx) {
     if (ctx->denoise_end) { (void)hipEventDestroy(ctx->denoise_end); }
     for (auto &slot : ctx->staging) { slot.release(); }
     for (auto timer : {&ctx->raycast_timer, &ctx->radiance_timer, &ctx->surface_timer, &ctx->bsdf_timer, &ctx->light_timer, &ctx->camera_timer,
-                       &ctx->instance_timer, &ctx->mesh_timer}) {
+                       &ctx->instance_timer, &ctx->mesh_timer, &ctx->lightmap_timer, &ctx->gather_timer}) {
         timer_destroy(*timer);
     }
-    ctx->update_stage.release(), ctx->update_scratch.release(), ctx->surface_meshes.release();
+    ctx->update_stage.release(), ctx->update_scratch.release(), ctx->surface_meshes.release(), ctx->lightmap_owner.release(), ctx->gather_table.release();
     ctx->spill.release(), ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->wf_counts.release(), ctx->wf_accum.release();
     ctx->pool.release(), ctx->counters.release(), ctx->work_counter.release(), ctx->scene_record.release();
     if (ctx->ev_begin) { (void)hipEventDestroy(ctx->ev_begin); }

@@ -15,6 +15,8 @@
 //   lrhip_bsdf.hip       BSDF queries: the closure evaluated or sampled at caller-supplied hits (bsdf_kernel.h)
 //   lrhip_light.hip      light queries: the emitters sampled from, or evaluated at, caller-supplied hits (light_kernel.h)
 //   lrhip_camera.hip     camera, sampler and film queries: sampler streams, camera rays, splats into the film (camera_kernel.h)
+//   lrhip_gather.hip     the gather vertex query: the plan of one irradiance sample at caller-supplied points (gather_vertex.h, gather_kernel.h)
+//   lrhip_lightmap.hip   the UV rasteriser of lightmap baking: texel records of one instance's UV chart (lightmap_kernels.h)
 //   lrhip_instance_update.hip  moving instances on the device: re-bake, refit and re-quantise (instance_update_kernels.h); the table test hook
 //   lrhip_mesh_update.hip      deforming a mesh on the device: vertex write, normal recompute, marking (mesh_update_kernels.h), then the re-bake and refit
 // Written for gfx950 only; no host fallback exists -- without a HIP device every entry point fails with LRHIP_ERROR_DEVICE.
@@ -211,6 +213,14 @@ struct lrhip_ctx {
     lrh::DeviceBuffer surface_meshes;
     bool surface_meshes_ready{false};
     uint32_t closure_features{0u};
+    // the UV rasteriser (lrhip_lightmap.hip): the owner word per texel of the last call's map; grows on demand and outlives the scene
+    lrh::DeviceBuffer lightmap_owner;
+    // lrd::GatherTable of the gather launch in flight (lrhip_gather.hip), written on the context's stream ahead of every launch
+    lrh::DeviceBuffer gather_table;
+    // handle[0] of every instance record as lrhip_upload_scene / lrhip_update_scene wrote it (the mesh index and the shape's property flags;
+    // no device update changes it): the rasteriser needs no read-back
+    std::vector<uint32_t> instance_handles;
+    lrh::Timer lightmap_timer, gather_timer;// (gather_timer: the gather vertex query's, lrhip_gather.hip)
 };
 
 namespace lrh {

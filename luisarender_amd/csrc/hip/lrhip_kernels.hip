@@ -26,6 +26,7 @@ constexpr uint32_t kListedVariants[] = {LR_VARIANT_LIST(LR_MASK)};
 constexpr uint32_t kListedPadded[] = {LR_PADDED_LIST(LR_MASK)};
 constexpr uint32_t kListedAov[] = {LR_AOV_LIST(LR_MASK)};
 constexpr uint32_t kListedQuery[] = {LR_QUERY_LIST(LR_MASK)};
+constexpr uint32_t kListedGather[] = {LR_GATHER_LIST(LR_MASK)};
 #undef LR_MASK
 constexpr bool scene_variants_are_listed() {
     for (auto scene : lrd::kSceneVariants) {
@@ -51,6 +52,9 @@ static_assert(all_carry(kListedAov, lrd::kFeatAov | lrd::kFeatSceneMask),
     "variants.h: LR_AOV_LIST holds kFeatAov kernels on the all-closures mask");
 static_assert(all_carry(kListedQuery, lrd::kFeatQuery | lrd::kFeatSceneMask),
     "variants.h: LR_QUERY_LIST holds kFeatQuery kernels on the all-closures mask");
+static_assert(all_carry(kListedGather, lrd::kFeatGather | lrd::kFeatQuery | lrd::kFeatSceneMask) && !all_carry(kListedGather, lrd::kFeatCount) &&
+                  sizeof(kListedGather) / sizeof(kListedGather[0]) == 4u,
+    "variants.h: LR_GATHER_LIST holds the four kFeatGather kernels on top of the query kernels' all-closures mask, without counting twins");
 }// namespace
 
 const KernelEntry *find_kernel(uint32_t mask, bool heavy) {

@@ -429,6 +429,9 @@ int upload_scene_tables(lrhip_ctx *ctx, const lr_scene *s) {
     LR_UP(upload(ctx, &s->filter, 1u, &d.filter));
     auto instances = build_instances(s);
     LR_UP(upload(ctx, instances.data(), instances.size(), &d.instances));
+    // (what lrhip_lightmap_texels reads an instance's mesh and property flags from: the device record's first word, kept on the host)
+    ctx->instance_handles.resize(instances.size());
+    for (size_t i = 0u; i < instances.size(); i++) { ctx->instance_handles[i] = instances[i].handle[0]; }
     {
         std::string error;
         auto shade = build_shade_tris(s, instances, error);
@@ -572,6 +575,8 @@ int lrhip_update_scene(lrhip_ctx *ctx, const lr_scene *s) {
     auto padded = build_padded_triangles(s);
     LR_HIP_CHECK(copy(d.bvh_tris, padded.data(), padded.size()));
     LR_HIP_CHECK(copy(d.instances, instances.data(), instances.size() * sizeof(instances[0])));
+    ctx->instance_handles.resize(instances.size());
+    for (size_t i = 0u; i < instances.size(); i++) { ctx->instance_handles[i] = instances[i].handle[0]; }
     LR_HIP_CHECK(copy(d.shade_tris, shade.data(), shade.size() * sizeof(shade[0])));
     // the fp32 boxes a later lrhip_set_instance_transforms refits from: the host's tables win again
     LR_HIP_CHECK(copy(ctx->nodes32, s->accel.nodes, static_cast<size_t>(s->accel.node_count) * sizeof(lr_bvh4_node)));

@@ -21,6 +21,8 @@
 #pragma once
 #include "dev_wavefront.h"
 #include "raycast_kernel.h"// (raycast_ray_valid: the screening of a caller's ray)
+#include "bsdf_kernel.h"   // (bsdf_resolve_hit: a gather record's point, the BSDF queries' own)
+#include "gather_vertex.h" // (the kFeatGather prologue's vertex)
 
 namespace lrd {
 
@@ -142,7 +144,8 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
     constexpr bool COUNT = (F & kFeatCount) != 0u, PCG = (F & kFeatGeneric) != 0u, ENV = (F & kFeatEnv) != 0u,
                    ALPHA = (F & kFeatAlpha) != 0u, DISNEY = (F & kFeatDisney) != 0u, MIX = (F & kFeatMix) != 0u,
                    LAYERED = (F & kFeatLayered) != 0u, AUX = (F & kFeatAux) != 0u, WF = (F & kFeatWf) != 0u, CONT = (F & kFeatCont) != 0u,
-                   AOV = (F & kFeatAov) != 0u, QUERY = (F & kFeatQuery) != 0u;
+                   AOV = (F & kFeatAov) != 0u, QUERY = (F & kFeatQuery) != 0u, GATHER = (F & kFeatGather) != 0u;
+    static_assert(!GATHER || (QUERY && !COUNT), "the gather kernel is the query kernel with another prologue; it has no counting twin");
     static_assert(!AOV || (MIX && LAYERED && !AUX && !WF), "the AOV kernel is the all-closures one-path-per-lane kernel");
     static_assert(!QUERY || (MIX && LAYERED && !AUX && !WF && !AOV), "the query kernel is the all-closures one-path-per-lane kernel");
     static_assert(!LAYERED || DISNEY, "the Layered interpreter instantiates the Disney closure");
@@ -503,6 +506,50 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                         sampler.restore(scene, words);
                         path_open = true;
                     }
+                } else if constexpr (GATHER) {
+                    // a path that starts AT a surface point: record 64 * tile_index + (k & 63) of the batch (two dwordx4 loads, resolved by the
+                    // BSDF queries' bsdf_resolve_hit; or a bare point and a normal.  What the records need beyond the query's columns -- the normals, the
+                    // mesh table and the counts that bound a record's ids -- is the GatherTable record args.pool points to: RenderArgs keeps
+                    // its layout, so that no other kernel's arguments move), sample s_begin + (k >> 6) of the record's stream, started as
+                    // the query prologue below starts it.  gather_vertex makes the shading block's vertex for a white Lambert surface there and
+                    // the lane is left as if it had just shaded it, the way the CONT prologue leaves a lane.  An invalid record starts no
+                    // path: n stays as it is.  A vertex that starts no ray at all (max_depth = 0; a failed light sample with a dead direction)
+                    // is a complete path of radiance 0: it is counted here and now
+                    const auto index = tile_index * 64u + (k & 63u);
+                    if (need && k < q_total && index < args.query_count) {
+                        pixel = film_tile + (k & 63u);
+                        const auto &table = *reinterpret_cast<const GatherTable *>(args.pool);
+                        const auto normals = table.normals;
+                        const BsdfArgs hit_args{args.query_rays, nullptr, nullptr, nullptr, table.meshes,
+                                                args.query_count, table.triangle_count, table.instance_count, table.mesh_count};
+                        SurfacePoint it{};
+                        auto valid = false;
+                        if (normals != nullptr) {
+                            const auto p = args.query_rays[index], n = normals[index];
+                            valid = raycast_finite(p.x) && raycast_finite(p.y) && raycast_finite(p.z) && raycast_finite(n.x) && raycast_finite(n.y) &&
+                                    raycast_finite(n.z) && ((__float_as_uint(n.x) | __float_as_uint(n.y) | __float_as_uint(n.z)) & 0x7fffffffu) != 0u;
+                            if (valid) {
+                                it.p = mk3(p.x, p.y, p.z);
+                                it.ng = surface_unit_direction(mk3(n.x, n.y, n.z));
+                                it.shading = frame_from_normal(it.ng);
+                            }
+                        } else {
+                            f3 wo_unused;
+                            valid = bsdf_resolve_hit(scene, hit_args, index, it, wo_unused);
+                        }
+                        if (valid) {
+                            const auto j = args.query_streams != nullptr ? args.query_streams[index] : args.query_stream_base + index;
+                            gather_start_stream(scene, sampler, j, s_begin + (k >> 6u));
+                            const auto g = normals != nullptr ? gather_vertex<true>(scene, it, sampler) : gather_vertex<false>(scene, it, sampler);
+                            ray = g.ray, shadow = g.shadow;
+                            nee = g.nee, beta = g.beta, pdf_bsdf = g.pdf_bsdf;
+                            Li = mk3(0.f);
+                            depth = 0u;
+                            want_shadow = g.want_shadow, want_closest = g.want_closest;
+                            path_open = want_shadow || want_closest;
+                            if (!path_open) { film_accumulate(pixel, mk3(0.f), scene.film_clamp); }
+                        }
+                    }
                 } else if constexpr (QUERY) {
                     // the same prologue with the caller's ray in place of camera.generate_ray: ray 64 * tile_index + (k & 63) of the batch, sample
                     // s_begin + (k >> 6).  The sampler is the one of pixel (j mod W, (j div W) mod H) for the ray's stream id j, moved past what
@@ -589,6 +636,9 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
             }
             if (!lr_any(tr.phase != kPhaseIdle)) {
                 if (PARK_HEAVY && lr_any(parked)) { continue; }// parked paths are left: shade them now
+                // (a gather vertex may start no ray at all -- its path is complete in the prologue -- so a round in which no lane traces is
+                // not the end of the item while samples are left: q_next grows by every idle lane each round, so this ends)
+                if (GATHER && q_next < q_total) { continue; }
                 break;// every lane of the tile is out of samples
             }
             // ==== (B) traverse until `refill` lanes have results to shade

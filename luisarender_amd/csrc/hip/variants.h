@@ -52,8 +52,12 @@
 // for them by mask, lrhip_render never does
 #define LR_QUERY_LIST(X) X(65660) X(65661) X(65662) X(65663) X(66172) X(66173) X(66174) X(66175)
 
+// irradiance gathers (kFeatGather = 131072 on top of kFeatQuery, lrhip_gather_irradiance): the all-closures scene mask with its
+// generic-sampler twin, and once more with kFeatNest.  No counting twins.  lrhip_gather_irradiance asks for them by mask
+#define LR_GATHER_LIST(X) X(196732) X(196734) X(197244) X(197246)
+
 // every object built from megapath_variant.hip
-#define LR_MEGAKERNEL_LIST(X) LR_VARIANT_LIST(X) LR_PADDED_LIST(X) LR_AOV_LIST(X) LR_QUERY_LIST(X)
+#define LR_MEGAKERNEL_LIST(X) LR_VARIANT_LIST(X) LR_PADDED_LIST(X) LR_AOV_LIST(X) LR_QUERY_LIST(X) LR_GATHER_LIST(X)
 
 // the heavy-closure kernels of wavefront mode (heavy_kernel.h; heavy_variant.hip, -DLR_HVARIANT=<mask>): bit 0 counters, bit 1 generic sampler,
 // bits 2-3 the closure kind (0 Disney, 4 Mix, 8 Layered), 512 Mix / Layered nested in each other

@@ -177,6 +177,7 @@ uint64_t lrhost_sizeof(const char *name) {
     LR_SIZEOF(lrhip_surface_point) LR_SIZEOF(lrhip_surface_query_params)
     LR_SIZEOF(lrhip_bsdf_result) LR_SIZEOF(lrhip_bsdf_query_params)
     LR_SIZEOF(lrhip_light_result) LR_SIZEOF(lrhip_light_query_params)
+    LR_SIZEOF(lrhip_gather_vertex) LR_SIZEOF(lrhip_gather_vertex_params) LR_SIZEOF(lrhip_gather_params)
     LR_SIZEOF(lrhip_sampler_query_params) LR_SIZEOF(lrhip_camera_sample) LR_SIZEOF(lrhip_camera_query_params) LR_SIZEOF(lrhip_film_splat_params)
 #undef LR_SIZEOF
     return 0u;

@@ -283,6 +283,88 @@ def _query_array(prefix: str, name: str, a, shapes, dtype_name: str, device: int
     return kind
 
 
+def check_irradiance_args(hits=None, points=None, normals=None, spp: int = 1, spp_begin: int = 0, streams=None, clamp=None, accumulate_into=None,
+                          device: int | None = None) -> str:
+    """What MegaPathRenderer.irradiance accepts (no device needed): the records and streams of check_gather_args; spp, spp_begin >= 0 integers
+    with spp_begin + spp < 2^32; clamp None or a positive finite number; accumulate_into None or a float32 raw result [N, 4] of the records'
+    kind (and device), contiguous.  Returns check_rays' answer; TypeError / ValueError as check_gather_args."""
+    kind = check_gather_args(hits, points, normals, 0, streams, device)
+    if isinstance(spp, bool) or isinstance(spp_begin, bool) or not isinstance(spp, (int, np.integer)) or not isinstance(spp_begin, (int, np.integer)):
+        raise ValueError("gather: spp and spp_begin must be integers")
+    if spp < 0 or spp_begin < 0 or spp_begin + spp > 0xFFFFFFFF:
+        raise ValueError(f"gather: samples [{spp_begin}, {spp_begin} + {spp}) are not a range of 32-bit sample indices")
+    if clamp is not None and not (0.0 < float(clamp) < float("inf")):
+        raise ValueError(f"gather: clamp must be a positive finite number or None (the scene's film clamp), not {clamp}")
+    if accumulate_into is not None:
+        records = points if points is not None else (hits.buffer if isinstance(hits, RayHits) else hits)
+        _query_array("gather", "accumulate_into", accumulate_into, ((None, 4),), "float32", device, records)
+    return kind
+
+
+def check_gather_args(hits=None, points=None, normals=None, sample: int = 0, streams=None, device: int | None = None) -> str:
+    """What MegaPathRenderer.gather_vertex accepts (no device needed).  Exactly one of hits -- a RayHits (a LightmapTexels is one), or a float32
+    [N, 8] array of lrhip_ray_hit records, as check_surface_args takes them -- and points -- float32 [N, 3] or [N, 4] world-space positions,
+    together with normals of the same shape rules (any length but 0); normals without points are refused.  An [N, 4] array must be
+    contiguous (it is read in place), an [N, 3] one is padded by a copy.  sample: an integer in [0, 2^32); streams: None or uint32 (torch:
+    int32, read as uint32) [N], contiguous.  All arrays are of one kind (numpy, or torch on one GPU) and have the same N.  Returns
+    check_rays' answer; TypeError for an argument that is no array or tensor at all, ValueError for anything else."""
+    def is_array(a):
+        return isinstance(a, np.ndarray) or (type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr"))
+
+    buffer = hits.buffer if isinstance(hits, RayHits) else hits
+    for name, a in (("hits", buffer), ("points", points), ("normals", normals), ("streams", streams)):
+        if a is not None and not is_array(a):
+            raise TypeError(f"gather: {name} must be a numpy array or a torch tensor, not {type(a).__name__}")
+    if (hits is None) == (points is None):
+        raise ValueError("gather: hits or points, one of them")
+    if (points is None) != (normals is None):
+        raise ValueError("gather: points and normals go together")
+    if isinstance(sample, bool) or not isinstance(sample, (int, np.integer)) or not 0 <= int(sample) <= 0xFFFFFFFF:
+        raise ValueError(f"gather: sample must be an integer in [0, 2^32), not {sample!r}")
+    if points is not None:
+        for name, a in (("points", points), ("normals", normals)):
+            if a.ndim != 2 or a.shape[1] not in (3, 4):
+                raise ValueError(f"gather: {name} must have shape [N, 3] or [N, 4], not {tuple(a.shape)}")
+        kinds = []
+        for name, a, like in (("points", points, None), ("normals", normals, points)):
+            if a.shape[1] == 4:  # read in place
+                kinds.append(_query_array("gather", name, a, ((None, 4),), "float32", device, like))
+            else:
+                kinds.append(_rows_kind("gather", name, a, device, like))
+        kind = kinds[0]
+        records = points
+    else:
+        kind = check_surface_args(hits, None, device, prefix="gather")
+        records = buffer
+    if streams is not None:
+        _query_array("gather", "streams", streams, ((None,),), "uint32", device, records)
+    return kind
+
+
+def _rows_kind(prefix: str, name: str, a, device: int | None, like=None) -> str:
+    # a float32 [N, 3] array (padded by a copy later: any strides) of `like`'s kind, device and N; returns its kind
+    if isinstance(a, np.ndarray):
+        kind, is_float32 = "numpy", a.dtype == np.float32
+    else:
+        import torch
+        kind, is_float32 = "torch", a.dtype == torch.float32
+        if a.device.type != "cuda":
+            raise ValueError(f"{prefix}: the {name} tensor is on {a.device}, not on a GPU")
+        if device is not None and a.device.index != device:
+            raise ValueError(f"{prefix}: the {name} tensor is on {a.device}, the renderer on GPU {device}")
+    if not is_float32:
+        raise ValueError(f"{prefix}: {name} must be float32, not {a.dtype}")
+    if like is not None:
+        like_kind = "numpy" if isinstance(like, np.ndarray) else "torch"
+        if kind != like_kind:
+            raise ValueError(f"{prefix}: {name} is a {kind} array, the other arrays are {like_kind} arrays")
+        if kind == "torch" and a.device != like.device:
+            raise ValueError(f"{prefix}: {name} is on {a.device}, the other arrays on {like.device}")
+        if int(a.shape[0]) != int(like.shape[0]):
+            raise ValueError(f"{prefix}: {int(a.shape[0])} rows of {name} for {int(like.shape[0])} records")
+    return kind
+
+
 def check_sampler_args(state=None, pattern: str = "", streams=None, indices=None, count: int | None = None, sample: int = 0,
                        device: int | None = None) -> str:
     """What MegaPathRenderer.sampler_start (state None) / sampler_draw (state given) accept (no device needed).
@@ -447,6 +529,20 @@ def check_mesh_vertices(positions, normals=None, mesh: int = 0, first: int = 0, 
     return kind
 
 
+def check_lightmap_args(instance, width, height, instance_count: int | None = None) -> int:
+    """What MegaPathRenderer.lightmap_texels accepts (no device needed): instance, width and height are integers (no bools, no floats) in
+    [0, 2^32), instance < instance_count where the caller knows it, and width * height <= 2^31 - 1, the most records one call takes.
+    Returns the number of texels; ValueError for anything else."""
+    for name, value in (("instance", instance), ("width", width), ("height", height)):
+        if not isinstance(value, (int, np.integer)) or isinstance(value, bool) or not 0 <= int(value) <= 0xFFFFFFFF:
+            raise ValueError(f"lightmap: {name} must be an integer in [0, 2^32), not {value!r}")
+    if instance_count is not None and int(instance) >= int(instance_count):
+        raise ValueError(f"lightmap: instance {instance} out of range ({int(instance_count)} instances)")
+    if int(width) * int(height) > 0x7FFFFFFF:
+        raise ValueError(f"lightmap: {width} x {height} texels are more than the 2^31 - 1 records of one call")
+    return int(width) * int(height)
+
+
 class RayHits:
     """Closest hits of MegaPathRenderer.trace: views (no copies) of ONE [N, 8] 32-bit buffer of lrhip_ray_hit records -- `buffer`, a
     float32 numpy array or, for the torch path, the float32 tensor on the device.  t (+inf: a miss), u, v: float32; inst, prim, tri:
@@ -471,6 +567,34 @@ class RayHits:
 
     def __len__(self) -> int:
         return int(self.buffer.shape[0])
+
+
+class LightmapTexels(RayHits):
+    """Texel records of MegaPathRenderer.lightmap_texels: RayHits (t = 0, tri = 0xffffffff: a point without a ray) that surface(),
+    bsdf_evaluate / bsdf_sample and light_sample take as they stand, record j * width + i for texel (i, j), and `flags`, a view of word 6 of
+    the same buffer: _ffi.LIGHTMAP_TEXEL_CENTRE (the centre lies in the owner triangle) or LIGHTMAP_TEXEL_TOUCHED (conservative: only the
+    texel's square meets it); 0 with the miss record for a texel nobody owns.  covered = hit; centre, touched: the flag bits as bool."""
+
+    def __init__(self, buffer, width: int, height: int):
+        super().__init__(buffer)
+        self.width, self.height = int(width), int(height)
+        if isinstance(buffer, np.ndarray):
+            self.flags = buffer.view(np.uint32)[:, 6]
+        else:
+            import torch
+            self.flags = buffer.view(torch.int32)[:, 6]
+
+    @property
+    def covered(self):
+        return self.hit
+
+    @property
+    def centre(self):
+        return (self.flags & _ffi.LIGHTMAP_TEXEL_CENTRE) != 0
+
+    @property
+    def touched(self):
+        return (self.flags & _ffi.LIGHTMAP_TEXEL_TOUCHED) != 0
 
 
 class SurfacePoints:
@@ -568,6 +692,26 @@ class LightSamples(LightResults):
     def __init__(self, rays, buffer):
         super().__init__(buffer)
         self.rays = rays
+
+
+class GatherVertices:
+    """Results of MegaPathRenderer.gather_vertex: views (no copies) of ONE [N, 24] float32 buffer of lrhip_gather_vertex records -- `buffer`, a
+    numpy array or, for the torch path, the tensor on the device.  rays, shadow: [N, 8] (ox, oy, oz, t_min, dx, dy, dz, t_max), strided views
+    (trace() wants np.ascontiguousarray / .contiguous() of them); nee, beta: [N, 3]; light_pdf, pdf: [N]; valid: bool, false for the invalid
+    record (pdf = 0 and a zero direction)."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        self.rays, self.shadow = buffer[:, 0:8], buffer[:, 8:16]
+        self.nee, self.light_pdf = buffer[:, 16:19], buffer[:, 19]
+        self.beta, self.pdf = buffer[:, 20:23], buffer[:, 23]
+
+    @property
+    def valid(self):
+        return (self.rays[:, 4:7] != 0).any(1) if isinstance(self.buffer, np.ndarray) else (self.rays[:, 4:7] != 0).any(dim=1)
+
+    def __len__(self) -> int:
+        return int(self.buffer.shape[0])
 
 
 class CameraRays:
@@ -1053,6 +1197,89 @@ class MegaPathRenderer:
     def last_mesh_update_ms(self) -> float:
         """lrhip_last_mesh_update_ms: HIP-event time of the kernels of the last set_mesh_vertices()"""
         return float(self._lib.lrhip_last_mesh_update_ms(self._ctx))
+
+    def gather_vertex(self, hits=None, points=None, normals=None, sample: int = 0, streams=None, sync: bool = True) -> GatherVertices:
+        """lrhip_query_gather_vertex (lrhip.h has the semantics): the plan of ONE irradiance sample at each record -- a path that starts at a
+        surface point: MegaPath's shading vertex for a virtual white Lambert surface there, with the throughput started at pi.  hits: a
+        RayHits from trace(), the LightmapTexels of lightmap_texels(), or [N, 8] records the caller made; or points with normals, float32
+        [N, 3] or [N, 4] (LRHIP_GATHER_FROM_POINTS: rays start at the point itself).  sample: the sample index; streams: the sampler stream
+        of each record (None: 0, 1, 2, ...; as in radiance()).  What check_gather_args accepts.  Returns GatherVertices: the irradiance sample
+        is (shadow unoccluded ? nee : 0) + beta x what `rays` finds, an emitter or the environment weighted by balance(pdf, its light pdf).
+        numpy arrays go through host pointers; torch tensors on this renderer's GPU are read in place (an [N, 3] array is padded by a copy)
+        and the result stays on the device (synchronisation as in trace())."""
+        a = _Arrays(check_gather_args(hits, points, normals, sample, streams, self._device), self._device)
+        records = a.pad(points, 4) if points is not None else (hits.buffer if isinstance(hits, RayHits) else hits)
+        n = int(records.shape[0])
+        p = _ffi.GatherVertexParams()
+        p.count, p.sample_index = n, int(sample)
+        p.flags = _ffi.GATHER_FROM_POINTS if points is not None else 0
+        out = a.empty((n, 24))
+        normals = a.pad(normals, 4) if normals is not None else None
+        p.records, p.normals, p.streams, p.out = a.ptr(records), a.ptr(normals), a.ptr(streams), a.ptr(out)
+        self._call(self._lib.lrhip_query_gather_vertex, p, a, sync)
+        return GatherVertices(out)
+
+    def irradiance(self, hits=None, points=None, normals=None, spp: int = 1, spp_begin: int = 0, streams=None, clamp: float | None = None,
+                   accumulate_into=None, raw: bool = False, sync: bool = True):
+        """lrhip_gather_irradiance (lrhip.h has the semantics): the irradiance at each record, samples [spp_begin, spp_begin + spp) of MegaPath's
+        estimator for paths that start AT the record's point -- next-event estimation at the point itself, then the scene's path tracing to
+        its depth -- on the device from end to end.  hits: a RayHits from trace(), the LightmapTexels of lightmap_texels(), or [N, 8] records;
+        or points with normals, float32 [N, 3] or [N, 4].  streams: the sampler stream of each record (None: 0, 1, 2, ...; stream py * W + px is
+        pixel (px, py)'s, so a map larger than the camera's frame repeats streams: correlated noise, unbiased mean).  clamp: per-sample clamp
+        (None: the scene's film clamp).  accumulate_into: a previous raw result, refined IN PLACE and returned.  What check_irradiance_args
+        accepts.  Returns the [N, 3] means sum / max(n, 1), or with raw the [N, 4] sums (sum r, sum g, sum b, n); n = 0 marks an invalid
+        record.  numpy arrays go through host pointers; torch tensors on this renderer's GPU are read in place and the result stays on the
+        device (synchronisation as in trace())."""
+        a = _Arrays(check_irradiance_args(hits, points, normals, spp, spp_begin, streams, clamp, accumulate_into, self._device), self._device)
+        records = a.pad(points, 4) if points is not None else (hits.buffer if isinstance(hits, RayHits) else hits)
+        n = int(records.shape[0])
+        p = _ffi.GatherParams()
+        p.count = n
+        p.spp_begin, p.spp_end = spp_begin, spp_begin + spp
+        p.clamp = 0.0 if clamp is None else clamp
+        p.flags = (_ffi.GATHER_ACCUMULATE if accumulate_into is not None else 0) | (_ffi.GATHER_FROM_POINTS if points is not None else 0)
+        out = accumulate_into if accumulate_into is not None else a.empty((n, 4))
+        normals = a.pad(normals, 4) if normals is not None else None
+        p.records, p.normals, p.streams, p.out = a.ptr(records), a.ptr(normals), a.ptr(streams), a.ptr(out)
+        if a.torch and n != 0 and (p.records % 16 != 0 or p.out % 16 != 0):
+            raise ValueError("gather: records and accumulate_into must be 16-byte aligned on the device")
+        self._call(self._lib.lrhip_gather_irradiance, p, a, sync)
+        if raw:
+            return out
+        if a.torch:
+            import torch
+            return out[:, :3] / torch.clamp(out[:, 3:4], min=1.0)
+        return out[:, :3] / np.maximum(out[:, 3:4], np.float32(1.0))
+
+    def last_gather_ms(self) -> float:
+        """lrhip_last_gather_ms: HIP-event time of the kernel(s) of the last irradiance() / gather_vertex()"""
+        return float(self._lib.lrhip_last_gather_ms(self._ctx))
+
+    def lightmap_texels(self, instance: int, width: int, height: int, conservative: bool = False, on_device: bool = False,
+                        sync: bool = True) -> LightmapTexels:
+        """lrhip_lightmap_texels (lrhip.h has the semantics): the UV rasteriser of a bake -- for each texel of a width x height lightmap over
+        the UV chart of instance `instance`, the point of the instance's mesh under the texel's centre ((i + 1/2) / width, (j + 1/2) / height),
+        as the record (inst, prim, u, v) without a ray that surface(), bsdf_sample() and light_sample() take.  Centre coverage by edge
+        functions, the lowest prim wins where charts overlap; conservative: a texel whose square only touches a triangle gets that triangle's
+        nearest point.  Texels nobody owns get the miss record.  instance, width, height: what check_lightmap_args accepts.  Returns
+        LightmapTexels over a [height * width, 8] buffer: numpy, or with on_device a float32 tensor on this renderer's GPU, written without a
+        copy through the host (synchronisation as in trace()).  A mesh without vertex UVs is a DeviceError."""
+        count = self._scene.view().instance_count if self._scene is not None else None
+        n = check_lightmap_args(instance, width, height, count)
+        a = _Arrays("torch" if on_device else "numpy", self._device)
+        out = a.empty((n, 8))
+        flags = (_ffi.LIGHTMAP_CONSERVATIVE if conservative else 0) | (_ffi.RAY_DEVICE_POINTERS if a.torch else 0)
+        if a.torch and sync:
+            import torch
+            torch.cuda.current_stream(torch.device("cuda", self._device)).synchronize()
+        self._check(self._lib.lrhip_lightmap_texels(self._ctx, int(instance), int(width), int(height), flags, a.ptr(out)))
+        if a.torch and sync:
+            self.synchronize()
+        return LightmapTexels(out, width, height)
+
+    def last_lightmap_ms(self) -> float:
+        """lrhip_last_lightmap_ms: HIP-event time of the kernels of the last lightmap_texels()"""
+        return float(self._lib.lrhip_last_lightmap_ms(self._ctx))
 
     def scene_table(self, which: int) -> np.ndarray:
         """tests / tools only (lrhip_read_scene_table): the bytes of one of the device tables that move with the geometry

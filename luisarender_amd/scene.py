@@ -145,6 +145,33 @@ class Scene:
         table = np.frombuffer(C.string_at(address, count * 32), np.float32).reshape(count, 8)
         return np.ascontiguousarray(table[:, 0:3]), np.ascontiguousarray(table[:, 3:6])
 
+    def mesh_uvs(self, mesh: int) -> np.ndarray:
+        """a copy of a mesh's vertex UVs -> [V, 2] float32 (what the UV rasteriser of MegaPathRenderer.lightmap_texels reads; meaningful where
+        the mesh's instances carry LR_SHAPE_HAS_VERTEX_UV)"""
+        view = self.view()
+        if not 0 <= int(mesh) < int(view.mesh_count):
+            raise ValueError(f"mesh_uvs: mesh {mesh} out of range ({int(view.mesh_count)} meshes)")
+        record = view.meshes[int(mesh)]
+        offset, count = int(record.vertex_offset), int(record.vertex_count)
+        if count == 0:
+            return np.zeros((0, 2), np.float32)
+        address = C.addressof(view.vertices.contents) + offset * 32
+        table = np.frombuffer(C.string_at(address, count * 32), np.float32).reshape(count, 8)
+        return np.ascontiguousarray(table[:, 6:8])
+
+    def mesh_triangles(self, mesh: int) -> np.ndarray:
+        """a copy of a mesh's triangles -> [T, 3] uint32, indices into the mesh's own vertices (mesh_vertices, mesh_uvs); row `prim` is the
+        triangle a hit or texel record names"""
+        view = self.view()
+        if not 0 <= int(mesh) < int(view.mesh_count):
+            raise ValueError(f"mesh_triangles: mesh {mesh} out of range ({int(view.mesh_count)} meshes)")
+        record = view.meshes[int(mesh)]
+        offset, count = int(record.triangle_offset), int(record.triangle_count)
+        if count == 0:
+            return np.zeros((0, 3), np.uint32)
+        address = C.addressof(view.triangles.contents) + offset * 12
+        return np.frombuffer(C.string_at(address, count * 12), np.uint32).reshape(count, 3).copy()
+
     def shutter_samples(self, camera: int = 0) -> list[tuple[float, float, int]]:
         """Camera::shutter_samples (src/base/camera.cpp:163-203) -> [(time, weight, spp)]"""
         out = []
