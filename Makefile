@@ -31,8 +31,8 @@ HOST_HDR := $(wildcard $(HOSTDIR)/*.h) $(wildcard include/*.h)
 HIP_SRC := $(wildcard $(HIPDIR)/lrhip_*.hip)
 HIP_HDR := $(wildcard $(HIPDIR)/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly nopair noride nostraight
-all: host oracle hip cli ieee shallow noearly nopair noride nostraight
+.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly nopair noride nostash nostraight
+all: host oracle hip cli ieee shallow noearly nopair noride nostash nostraight
 
 # oracle/_ref: the reference's OWN sources compiled in place against the scalar LuisaCompute stand-in of oracle/ref_shim
 # (test infrastructure: pins oracle/ to the reference; needs /root/reference, so only where the reference tree exists)
@@ -190,6 +190,14 @@ $(LIBDIR)/variants/liblrhip_nopair.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip
 noride: $(LIBDIR)/variants/liblrhip_noride.so
 $(LIBDIR)/variants/liblrhip_noride.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
 	$(MAKE) --no-print-directory hip-variant NAME=noride DEFS='-DLR_POOL_SHADOW_RIDE=0' VARIANT_MASKS='4096 4097 4098 4099 4100 4101 4102 4103 4116 4117 20482 20483 12308 12309' HEAVY_MASKS=
+
+# Pool kernels once more WITHOUT the path stash (megapool_kernel.h: LR_POOL_PATH_STASH): a context without a path starts one inside the shading block,
+# the hand-out loop and the camera code in nearly every batch for a quarter of its lanes.  The masks of `noride`.  TEST INFRASTRUCTURE: the stash changes
+# which lane and which batch start which sample number and nothing else, so the shipped library's frames and its path / ray / node / triangle /
+# shaded-vertex counters must equal this library's (tests/test_gpu_path_stash.py).
+nostash: $(LIBDIR)/variants/liblrhip_nostash.so
+$(LIBDIR)/variants/liblrhip_nostash.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
+	$(MAKE) --no-print-directory hip-variant NAME=nostash DEFS='-DLR_POOL_PATH_STASH=0' VARIANT_MASKS='4096 4097 4098 4099 4100 4101 4102 4103 4116 4117 20482 20483 12308 12309' HEAVY_MASKS=
 
 # Kernels once more WITHOUT the straight-line control flow of the traversal loop (dev_trace.h: LR_STRAIGHT_TAIL): the three pushes of a node step are
 # EXEC regions again and a closest hit is committed by selects on VCC.  The lean one-path kernels and every pool kernel but the continuation passes

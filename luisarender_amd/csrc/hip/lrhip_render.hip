@@ -96,10 +96,11 @@ bool wants_pool(const lrhip_ctx *ctx) {
         ctx->scene.sampler_spp));
 }
 // path state of the pool kernels: two contexts per thread, 4 (Independent sampler) | 5 float4 each and one more for the ids of a path
-// whose last shadow ray rides with the next one (LR_POOL_SHADOW_RIDE), [context][quad][thread] (megapool_kernel.h); sized for 6
+// whose last shadow ray rides with the next one (LR_POOL_SHADOW_RIDE), [context][quad][thread] (megapool_kernel.h); sized for 6.  Behind the
+// records, every wave's stash of started paths (LR_POOL_PATH_STASH): kPoolStashEntries entries of kPoolStashQuads float4, [wave][quad][entry]
 int ensure_pool(lrhip_ctx *ctx, uint32_t resident_blocks) {
-    return ensure(ctx->pool, static_cast<size_t>(resident_blocks) * lrd::kWavesPerBlock * lrd::kPoolSlots * lrd::kPoolRecordQuadsMax
-        * sizeof(float4));
+    return ensure(ctx->pool, static_cast<size_t>(resident_blocks) * lrd::kWavesPerBlock
+        * (lrd::kPoolSlots * lrd::kPoolRecordQuadsMax + lrd::kPoolStashEntries * lrd::kPoolStashQuads) * sizeof(float4));
 }
 
 }// namespace lrh

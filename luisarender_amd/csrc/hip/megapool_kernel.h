@@ -139,7 +139,31 @@ namespace lrd {
 // instructions unchanged; the wavefront passes' code objects byte-identical (their contexts keep the shadow-only job: RIDE below).
 #define LR_POOL_SHADOW_RIDE 1
 #endif
+#ifndef LR_POOL_PATH_STASH
+// PATH STASH (the pool kernels that `STASH` in megapool_kernel names: all but the wavefront passes and three sets that spilled more with it).  A context without a path used to start one inside the shading block: the hand-out loop, then
+// sampler.start, the filter's two alias picks, camera_ray -- in nearly every batch (a path starts once per 3.65 batch slots, a batch holds ~53), for about
+// a quarter of its lanes, with the registers of the vertex just shaded alive around it.  1 = paths are started 64 AT A TIME, by all lanes, right behind
+// the parking stores of a batch (a lane holds its other context's 19 words there and nothing of a vertex): the same hand-out loop gives 64 consecutive
+// sample numbers to the 64 lanes, each lane runs the unchanged start code and stores what it produced -- camera ray, filter weight, pixel index, work item,
+// pixel in tile, the sampler's state behind the camera draws -- into the wave's STASH in global memory, a ring of kPoolStashEntries entries, field-major
+// [quad][entry] (a fill stores coalesced, lanes of consecutive rank load coalesced), behind the records in RenderArgs::pool.  The stash is filled before a
+// batch whenever it holds fewer entries than the batch has lanes that shade (and the launch has samples left); inside the block a context that needs a
+// path takes entry head + its rank among the asking lanes: four loads, then exactly what used to follow the camera code.  Head and count are wave-uniform.
+// Every path's random numbers, rays and float operations are unchanged; which lane and which batch start a sample number are not, and a wave may walk
+// into its next work item up to 127 samples earlier (LR_POOL_FILM_ADD takes a path whose item the wave has left): films and the path / ray / node /
+// triangle / shaded-vertex counters are bit-identical (tests/test_gpu_path_stash.py, against `make nostash`).  0 = the former code.  Against the commit
+// before, three runs a side alternating (profiles/path_stash_ab.txt): C2 1309.3 -> 1332.5 Msamples/s (+ 1.77 %, the runs of a side 0.10 - 0.14 % apart), C3 1290 ->
+// 1322, C4 1596 -> 1611, C2 under PaddedSobol 1221 -> 1241; path regeneration 0.054 -> 0.028 of a wave's life, VALU wave instructions per sample 536 -> 529, HBM
+// traffic + 7.8 % (the rings of 4096 waves are the size of the L2s); lanes.trace_starved and the gain at 64 spp as at 1024: the fill is not capped near the
+// end of a launch.  <4096> still at 128 VGPRs without a spill; which kernels take the stash, and how they hold the work item: STASH in megapool_kernel.
+#define LR_POOL_PATH_STASH 1
+#endif
 constexpr uint32_t kPoolSlots = 128u;// paths per wave: two contexts per lane
+// LR_POOL_PATH_STASH: a wave's started paths, kPoolStashQuads float4 at [quad][entry], behind the records (lrhip_render.hip: ensure_pool)
+//   0  origin.xyz | t_min      1  direction.xyz | t_max      2  filter weight | pixel index (frame) | work item | pixel in tile
+//   3  the sampler's state behind the camera draws: word 0 (Independent), sample index | pixel (kFeatPadded), words 0-3 (run-time generic sampler)
+constexpr uint32_t kPoolStashEntries = 128u;// (a fill adds up to 64 to fewer than 64)
+constexpr uint32_t kPoolStashQuads = 4u;
 
 // ---- path state of one context in global memory: kPoolQuads float4 at [context][quad][thread]
 //   0  nee.xyz | pdf_bsdf        1  beta.xyz | depth (16) | pixel in tile (6) << 16 | pending (1) << 22
@@ -418,6 +442,32 @@ template<bool ENV>
         }                                                                                                                                        \
     } while (false)
 
+// The hand-out of sample numbers: lanes with `need` set take the next samples of the item's queue, in lane order.  A loop, because the wave may walk
+// into its next work item half way through, and because a pixel beyond the frame's edge has no samples: such a lane asks again.  Expanded inside the
+// shading block (the former code, the wavefront passes) and in the stash's fill (LR_POOL_PATH_STASH), a macro for the reason given above.
+#define LR_POOL_HAND_OUT()                                                                                                                       \
+            for (;;) {                                                                                                                           \
+                const auto mask = lr_ballot(need);                                                                                               \
+                if (mask == 0ull) { break; }                                                                                                     \
+                if (q_next >= q_total) {/* the item's queue is dry: on to the next item, the old one's paths finish beside the new one's */      \
+                    if (!items_left) { break; }                                                                                                  \
+                    take_item();                                                                                                                 \
+                    if (!items_left) { break; }                                                                                                  \
+                    continue;                                                                                                                    \
+                }                                                                                                                                \
+                const auto avail = q_total - q_next;                                                                                             \
+                const auto rank = lane_rank(mask);                                                                                               \
+                if (need && rank < avail) {                                                                                                      \
+                    const auto k = q_next + rank;                                                                                                \
+                    const auto px = tx * 8u + (k & 7u), py = ty * 8u + ((k >> 3u) & 7u);                                                         \
+                    if (CONT || (px < scene.camera.width && py < scene.camera.height)) {                                                         \
+                        new_k = k, new_item = item, new_px = px, new_py = py, new_s = s_begin + (k >> 6u);                                       \
+                        got = true, need = false;                                                                                                \
+                    }                                                                                                                            \
+                }                                                                                                                                \
+                q_next += min(static_cast<uint32_t>(__popcll(mask)), avail);                                                                     \
+            }
+
 template<uint32_t F>
 __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(DScenePtr scene_ptr, RenderArgs args) {
     const DScene &scene = *(const DScene *)scene_ptr;
@@ -445,6 +495,12 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
     constexpr bool RIDE = LR_POOL_SHADOW_RIDE != 0 && !WF;// (the wavefront passes keep the shadow-only job)
     constexpr uint32_t RECORD = QUADS + (RIDE ? 1u : 0u);  // quads of a context's record: quad QUADS holds the ids of a path whose last shadow ray rides along
     static_assert(RECORD <= kPoolRecordQuadsMax, "ensure_pool sizes the records");
+    // LR_POOL_PATH_STASH: every pool kernel but the wavefront passes -- and but the ones whose register allocation came out with more spilled VGPRs than
+    // the former code's whichever way the work item is held (below): the alpha-tested set, environment + generic sampler without Disney, and environment
+    // + Disney with float texels under the Independent sampler.  They start their paths inside the block as before (profiles/path_stash_ab.txt, section 3).
+    constexpr bool STASH = LR_POOL_PATH_STASH != 0 && !WF && !ALPHA && !(ENV && PCG && !DISNEY) && !(ENV && DISNEY && !PCG && (F & kFeatByteTex) == 0u);
+    // ... and the work item as a scalar (take_item) where that is the allocation with fewer spills: the kernels without an environment
+    constexpr bool STASH_SCALAR_ITEM = STASH && !ENV;
     __shared__ uint32_t s_stack[kStackLds * kBlockThreads];
     __shared__ float4 s_stage[kWavesPerBlock * kStageWave];// 4 KiB of node packets per wave
 #if LR_POOL_PARK_ON_STACK == 0
@@ -489,6 +545,10 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
     auto q_next = 0u, q_total = 0u;// the item's sample queue: k = 64 * (s - s_begin) + pixel_in_tile (CONT: record item * item_records + k)
     auto s_begin = 0u, s_count = 0u, tx = 0u, ty = 0u;
     if (!CONT) { film_tile[lane * 3u] = 0ull, film_tile[lane * 3u + 1u] = 0ull, film_tile[lane * 3u + 2u] = 0ull; }
+    // LR_POOL_PATH_STASH: the wave's ring of started paths (wave-uniform: entries [stash_head, stash_head + stash_count) modulo kPoolStashEntries wait)
+    [[maybe_unused]] auto stash_head = 0u, stash_count = 0u;
+    [[maybe_unused]] const auto stash = args.pool + static_cast<size_t>(2u * kPoolRecordQuadsMax) * args.total_threads +
+                                        static_cast<size_t>(blockIdx.x * kWavesPerBlock + wave_in_block) * (kPoolStashQuads * kPoolStashEntries);
     // ---- the lane: its ray in flight, the context the ray belongs to (`cur`) and the lane's other context (`oth`)
     TravState tr{};
     tr.phase = kPhaseIdle;
@@ -519,6 +579,10 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
     auto take_item = [&]() {
         flush_tile();
         item = next_item(CONT ? scene.wf.counts + kWfWorkCont : args.work_counter, item_count, lane);
+        // (LR_POOL_PATH_STASH: the item as a scalar -- to the compiler a shuffle's result differs from lane to lane, and with it the queue's words, the
+        // tile and the sample range stand in vector registers through the whole shading block: beside the stash's head and count <4096> spilled two.  The
+        // environment kernels have no scalar registers to spare -- there the eight words spill as scalars, which costs more -- and keep the vector form)
+        if constexpr (STASH_SCALAR_ITEM) { item = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(item))); }
         q_next = 0u, q_total = 0u, s_count = 0u;
         if (item == kInvalid) {
             items_left = false;
@@ -538,7 +602,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
     for (;;) {
         // ==== (A) shading batches, while they are due (pool_shade_due: enough lanes hold a context to shade)
         for (;;) {
-            const auto samples_left = items_left || q_next < q_total;
+            const auto samples_left = items_left || q_next < q_total || (STASH && stash_count != 0u);
             if (!pool_shade_due(tr.phase, cur.flags, oth.flags, samples_left)) { break; }
             const auto t_shade = COUNT ? __builtin_readcyclecounter() : 0ull;
             if (ALPHA) { tr.pend_t = 0.f, tr.pend_u = 0.f, tr.pend_v = 0.f; }// (no candidate waits for its alpha test out here: three registers the block need not carry)
@@ -585,6 +649,40 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                 park[4u * kBlockThreads] = tr.cur;
 #endif
                 asm volatile("" ::: "memory");// (the values must not be forwarded to the loads at the end of the block: they are to LEAVE the registers)
+            }
+            // ==== LR_POOL_PATH_STASH, the fill: the stash holds fewer started paths than this batch has lanes that shade, and the launch has samples
+            // left -- all 64 lanes take the next 64 sample numbers (fewer: the launch's last) and start their paths.  Here, because a lane holds its other
+            // context and the hand-out's scalars and nothing else: the camera code gets the registers the vertex code is about to use.
+            [[maybe_unused]] uint32_t t_fill = 0u;// (COUNT: cycles of this batch's fill)
+            if constexpr (STASH) {
+                // (the vote is taken as a scalar: the queue's words live in vector registers, and head and count are to stay wave-uniform to the compiler)
+                if (__builtin_amdgcn_readfirstlane(stash_count < static_cast<uint32_t>(__popcll(lr_ballot(mine))) && (items_left || q_next < q_total) ? 1 : 0) != 0) {
+                    const auto t_fill0 = COUNT ? __builtin_readcyclecounter() : 0ull;
+                    auto need = true, got = false;
+                    auto new_k = 0u, new_item = kInvalid, new_px = 0u, new_py = 0u, new_s = 0u;
+                    LR_POOL_HAND_OUT();
+                    const auto filled = lr_ballot(got);
+                    if (got) {// MegakernelPathTracingInstance::Li prologue, mega_path.cpp:52-62
+                        const auto entry = stash + ((stash_head + stash_count + lane_rank(filled)) & (kPoolStashEntries - 1u));
+                        PathSampler<PCG> first{};
+                        first.start(scene, new_px, new_py, new_s);
+                        const auto u_filter = first.next_pixel_2d();
+                        const auto u_lens = scene.camera.kind == LR_CAMERA_THIN_LENS ? first.next_2d() : f2{.5f, .5f};
+                        Ray camera{};
+                        float weight;
+                        camera_ray(scene, scene.filter, new_px, new_py, u_filter, u_lens, camera, weight);
+                        uint32_t words[kWfSamplerWordsMax] = {0u, 0u, 0u, 0u};
+                        first.save(words);
+                        entry[0u * kPoolStashEntries] = make_float4(camera.o.x, camera.o.y, camera.o.z, camera.t_min);
+                        entry[1u * kPoolStashEntries] = make_float4(camera.d.x, camera.d.y, camera.d.z, camera.t_max);
+                        entry[2u * kPoolStashEntries] = make_float4(weight, __uint_as_float(new_py * scene.camera.width + new_px), __uint_as_float(new_item), __uint_as_float(new_k & 63u));
+                        entry[3u * kPoolStashEntries] = PADDED ? make_float4(__uint_as_float(words[0]), __uint_as_float(words[3]), 0.f, 0.f)
+                                                               : make_float4(__uint_as_float(words[0]), __uint_as_float(words[1]), __uint_as_float(words[2]), __uint_as_float(words[3]));
+                    }
+                    stash_count += static_cast<uint32_t>(__popcll(filled));
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");// (entries are read by other lanes of the wave)
+                    if (COUNT) { t_fill = static_cast<uint32_t>(__builtin_readcyclecounter() - t_fill0); }
+                }
             }
             // ---- the context's path
             PathSampler<PCG> sampler{};
@@ -879,27 +977,39 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
             auto need = mine && (!path_open || final_shadow);// (a context without a path: it takes the next sample, if the launch has one left)
             auto got = false;
             auto new_k = 0u, new_item = kInvalid, new_px = 0u, new_py = 0u, new_s = 0u;
-            for (;;) {
+            if constexpr (STASH) {// the hand-out is the stash's: a lane that asks takes entry head + its rank among the asking lanes, while entries last
                 const auto mask = lr_ballot(need);
-                if (mask == 0ull) { break; }
-                if (q_next >= q_total) {// the item's queue is dry: on to the next item, the old one's paths finish beside the new one's
-                    if (!items_left) { break; }
-                    take_item();
-                    if (!items_left) { break; }
-                    continue;
-                }
-                const auto avail = q_total - q_next;
-                const auto rank = lane_rank(mask);
-                if (need && rank < avail) {
-                    const auto k = q_next + rank;
-                    const auto px = tx * 8u + (k & 7u), py = ty * 8u + ((k >> 3u) & 7u);
-                    if (CONT || (px < scene.camera.width && py < scene.camera.height)) {
-                        new_k = k, new_item = item, new_px = px, new_py = py, new_s = s_begin + (k >> 6u);
+                if (mask != 0ull && stash_count != 0u) {
+                    const auto rank = lane_rank(mask);
+                    if (need && rank < stash_count) {
+                        const auto entry = stash + ((stash_head + rank) & (kPoolStashEntries - 1u));
+                        const auto e0 = entry[0u * kPoolStashEntries], e1 = entry[1u * kPoolStashEntries], e2 = entry[2u * kPoolStashEntries], e3 = entry[3u * kPoolStashEntries];
                         got = true, need = false;
+                        sampler_left = false;// (the context takes another path: every quad of its record is written below)
+                        if (final_shadow) {// the ids of the path that ends leave for the extra quad
+                            if (LEAN_STATE) { load_ids(); }
+                            state_store(side, QUADS, make_float4(__uint_as_float(pixel_index), __uint_as_float(path_item), __uint_as_float(dp >> 16u), 0.f));
+                        }
+                        pixel_index = __float_as_uint(e2.y);
+                        path_item = __float_as_uint(e2.z);
+                        uint32_t words[kWfSamplerWordsMax] = {__float_as_uint(e3.x), 0u, 0u, 0u};
+                        if (PADDED) { words[3] = __float_as_uint(e3.y); }
+                        else if (PCG) { words[1] = __float_as_uint(e3.y), words[2] = __float_as_uint(e3.z), words[3] = __float_as_uint(e3.w); }
+                        sampler.restore(scene, words);
+                        ray.o = mk3(e0.x, e0.y, e0.z), ray.t_min = e0.w;
+                        ray.d = mk3(e1.x, e1.y, e1.z), ray.t_max = e1.w;
+                        beta = mk3(e2.x);
+                        if (!final_shadow) { Li = mk3(0.f), nee = mk3(0.f); }// (else: the old path's, in their words of the record until its shadow ray is traced)
+                        pdf_bsdf = 1e16f;
+                        dp = (__float_as_uint(e2.w) << 16u) | (final_shadow ? kPoolPending : 0u);
+                        path_open = true, want_shadow = final_shadow, want_closest = true;
+                        if (COUNT) { local.paths++; }
                     }
+                    const auto taken = min(static_cast<uint32_t>(__popcll(mask)), stash_count);
+                    stash_head = (stash_head + taken) & (kPoolStashEntries - 1u), stash_count -= taken;
                 }
-                q_next += min(static_cast<uint32_t>(__popcll(mask)), avail);
-            }
+            } else {// the former code (its lines as they were: the wavefront passes' code objects are held to the parent's)
+            LR_POOL_HAND_OUT();
             if (got) {
                 sampler_left = false;// (the context takes another path: every quad of its record is written below)
                 if (CONT) {// a path comes back from the heavy kernel: as if this context's vertex had just been shaded
@@ -941,6 +1051,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                     path_open = true, want_shadow = final_shadow, want_closest = true;
                     if (COUNT) { local.paths++; }
                 }
+            }
             }
             // ---- every context that goes on: its path state back into the record, its job's rays into the context
             const auto t_launch = COUNT ? __builtin_readcyclecounter() : 0ull;
@@ -1027,6 +1138,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                     local.shade_cycles += t_end - t_shade;
                     local.shade_closure_cycles += t_closure_sum, local.shade_regen_cycles += t_launch - t_regen;
                     local.shade_light_cycles += (t_regen - t_shade) - t_closure_sum;// everything of (A) that is not the closure section
+                    if constexpr (STASH) { local.shade_regen_cycles += t_fill, local.shade_light_cycles -= t_fill; }// (the fill starts paths: regeneration)
                 }
                 local.shade_calls++;
             }
@@ -1039,7 +1151,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
 #endif
         const auto t_trace = COUNT ? __builtin_readcyclecounter() : 0ull;
         for (;;) {
-            const auto for_alpha = pool_trace<COUNT, ALPHA>(scene, stack, tr, cur, oth, items_left || q_next < q_total, ts);
+            const auto for_alpha = pool_trace<COUNT, ALPHA>(scene, stack, tr, cur, oth, items_left || q_next < q_total || (STASH && stash_count != 0u), ts);
             if (!ALPHA) { break; }
             // (candidates may wait when the wave leaves for the shading block, too: no lane takes one into it)
             if (lr_any((tr.phase & kPhasePendingAlpha) != 0u)) { resolve_pending_alpha(scene, stack, tr); }
