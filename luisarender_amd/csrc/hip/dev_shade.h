@@ -516,7 +516,9 @@ LR_CALL float4 texture_eval_tables(const lr_texture *textures, const float *texe
     }
     auto decode = [&](float c, int ch) {// image.cpp:138-153
         // x^y through the hardware's log2 / exp2 (v_log_f32 / v_exp_f32, ~1 ulp each) instead of powf (158 instructions with the
-        // project's flags, four of them per lookup); x^2.4 = x^2 * x^0.4 keeps the exponent error small: ~3e-7 relative
+        // project's flags, four of them per lookup); x^2.4 = x^2 * x^0.4 keeps the exponent error small: 4.4e-7 relative at most over
+        // texels in [0, 2.5], measured against float64 (tests/texture_reference.py: MEASURED_SRGB).  The gamma branch takes g * log2(x) as it
+        // stands: the logarithm's ulp is scaled by g |log2 x|, 2.2e-6 relative at most for g <= 3 over the same texels (MEASURED_GAMMA)
         if (ti.encoding == LR_TEX_ENC_SRGB) {
             const auto x = (c + 0.055f) * (1.0f / 1.055f);
             c = c <= 0.04045f ? c * (1.0f / 12.92f) : x * x * __builtin_amdgcn_exp2f(0.4f * __builtin_amdgcn_logf(x));
