@@ -31,7 +31,7 @@ HOST_HDR := $(wildcard $(HOSTDIR)/*.h) $(wildcard include/*.h)
 HIP_SRC := $(wildcard $(HIPDIR)/lrhip_*.hip)
 HIP_HDR := $(wildcard $(HIPDIR)/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip oracle cli clean hip-variant variant-lib ref ieee shallow noearly nopair noride nostash nostraight
+.PHONY: all host hip oracle oracle-ulp cli clean hip-variant variant-lib ref ieee shallow noearly nopair noride nostash nostraight
 all: host oracle hip cli ieee shallow noearly nopair noride nostash nostraight
 
 # oracle/_ref: the reference's OWN sources compiled in place against the scalar LuisaCompute stand-in of oracle/ref_shim
@@ -51,6 +51,11 @@ oracle/liboracle.so: oracle/oracle.cpp $(wildcard oracle/*.h) include/lr_scene.h
 # the oracle's own frames (the lamp-lit fog case of the volumetric integrator, tests/test_gpu_parity.py); never a reference for anything else
 oracle/liboracle_fma.so: oracle/oracle.cpp $(wildcard oracle/*.h) include/lr_scene.h Makefile
 	$(CXX) $(ORACLE_FLAGS) -ffp-contract=fast -shared -o $@ oracle/oracle.cpp
+# the same oracle with every cosine and sine one ulp up (oracle_math.h: ORACLE_NUDGE_TRIG): TEST INFRASTRUCTURE for tests/vpt_paths.py, which
+# takes the paths that this moves out of its judgement of the `layered` case; never a reference for anything else
+oracle-ulp: oracle/liboracle_ulp.so
+oracle/liboracle_ulp.so: oracle/oracle.cpp $(wildcard oracle/*.h) include/lr_scene.h Makefile
+	$(CXX) $(ORACLE_FLAGS) -DORACLE_NUDGE_TRIG=1 -shared -o $@ oracle/oracle.cpp
 
 # The megakernel is precompiled for a curated set of feature masks, one object per mask so that they build in parallel (make -j).
 # csrc/hip/variants.h is the only place where the masks are written: the lists are read off its X-macros with the host preprocessor.

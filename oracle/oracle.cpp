@@ -382,7 +382,7 @@ struct oracle_ctx {
         return f3(m[0], m[1], m[2]) * v.x + f3(m[3], m[4], m[5]) * v.y + f3(m[6], m[7], m[8]) * v.z;
     }
     static float directional_pdf(float p, float theta) {// spherical.cpp:76-80
-        auto sn = std::sin(theta);
+        auto sn = o_sin(theta);
         auto inv_s = sn > 0.f ? 1.f / sn : 0.f;
         return p * inv_s * (.5f * inv_pi * inv_pi);
     }
@@ -447,7 +447,7 @@ struct oracle_ctx {
             auto cos_t = (1.f - u.x) + u.x * env.cos_half_angle;// sample_uniform_cone, sampling.cpp:123-131
             auto sin_t = std::sqrt(std::max(1.f - cos_t * cos_t, 0.f));
             auto phi = 2.f * pi * u.y;
-            auto wi_local = f3(sin_t * std::cos(phi), sin_t * std::sin(phi), cos_t);
+            auto wi_local = f3(sin_t * o_cos(phi), sin_t * o_sin(phi), cos_t);
             auto frame = Frame::make(f3(env.direction[0], env.direction[1], env.direction[2]));
             return {env_directional(env, wi_local), normalize(mul3(env.env_to_world, frame.local_to_world(wi_local)))};
         }
@@ -463,8 +463,8 @@ struct oracle_ctx {
         float2 uv{(static_cast<float>(sx.index) + sx.u) / static_cast<float>(W), (static_cast<float>(sy.index) + sy.u) / static_cast<float>(H)};
         auto p = env.pdf[sy.index * W + sx.index];
         auto phi = 2.f * pi * (1.f - uv.x), theta = pi * uv.y;// Spherical::uv_to_direction, spherical.cpp:42-50
-        auto sin_theta = std::sin(theta);
-        auto w = normalize(f3(std::sin(phi) * sin_theta, std::cos(theta), std::cos(phi) * sin_theta));
+        auto sin_theta = o_sin(theta);
+        auto w = normalize(f3(o_sin(phi) * sin_theta, o_cos(theta), o_cos(phi) * sin_theta));
         auto L = illuminant(*scene, env.emission_tex, uv).value * env.scale;
         return {{L, directional_pdf(p, theta)}, normalize(mul3(env.env_to_world, w))};
     }
@@ -729,7 +729,7 @@ struct oracle_ctx {
                                                        -1.f / (2.f * g) * (1.f + g * g - sqr((1.f - g * g) / (1.f + g - 2.f * g * up.x)));
                 auto sin_theta = std::sqrt(std::max(0.f, 1.f - cos_theta * cos_theta));
                 auto phi = 2.f * pi * up.y;
-                float3 wi{sin_theta * std::cos(phi), cos_theta, sin_theta * std::sin(phi)};
+                float3 wi{sin_theta * o_cos(phi), cos_theta, sin_theta * o_sin(phi)};
                 out.ray = Ray{ray.o + ray.d * t, 0.f, wi, std::numeric_limits<float>::max()};
                 auto pdf = pdf_channels * (sigma_t * Tr);
                 out.f = Tr * sigma_s, out.pdf = pdf.x + pdf.y + pdf.z;

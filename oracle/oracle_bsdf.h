@@ -116,7 +116,7 @@ struct TrowbridgeReitz {// :117-237
         }
         auto r = std::sqrt(U.x / (1.f - U.x));
         auto phi = (2.f * pi) * U.y;
-        return {r * std::cos(phi), r * std::sin(phi)};
+        return {r * o_cos(phi), r * o_sin(phi)};
     }
     static float3 sample(float3 wi, float2 alpha, float2 U) {// :210-231
         auto wiStretched = normalize(f3(alpha.x * wi.x, alpha.y * wi.y, wi.z));
@@ -606,7 +606,7 @@ struct DisneyClosure {
             auto cosTheta = std::sqrt(std::max(0.f, (1.f - std::pow(alpha2, 1.f - u.x)) / (1.f - alpha2)));
             auto sinTheta = std::sqrt(std::max(0.f, 1.f - cosTheta * cosTheta));
             auto phi = 2.f * pi * u.y;
-            auto wh = f3(sinTheta * std::cos(phi), sinTheta * std::sin(phi), cosTheta);
+            auto wh = f3(sinTheta * o_cos(phi), sinTheta * o_sin(phi), cosTheta);
             wh = same_hemisphere(wo, wh) ? wh : -wh;
             wi = reflect(-wo, wh);
             valid = same_hemisphere(wo, wi);
@@ -787,7 +787,7 @@ struct Closure {
         auto sin_t = std::sqrt(1.f - sqr(cos_t));
         auto phi = 2.f * pi * u.y;
         auto frame = Frame::make(wo);
-        auto wi = frame.local_to_world(f3(sin_t * std::cos(phi), sin_t * std::sin(phi), cos_t));
+        auto wi = frame.local_to_world(f3(sin_t * o_cos(phi), sin_t * o_sin(phi), cos_t));
         pdf = hg(cos_t, g);
         return wi;
     }

@@ -62,6 +62,16 @@ inline float3 cross(float3 a, float3 b) {
 inline float length(float3 a) { return std::sqrt(dot(a, a)); }
 inline float3 normalize(float3 a) { return a * (1.0f / std::sqrt(dot(a, a))); }
 inline float sqr(float x) { return x * x; }
+// Every cosine and sine of the oracle.  ORACLE_NUDGE_TRIG (oracle/liboracle_ulp.so, Makefile): each comes back one ulp further up -- what
+// another libm, the device's, may return for the same argument.  TEST INFRASTRUCTURE for tests/vpt_paths.py: a path whose radiance this moves
+// (a Layered surface seeds its walk from the BITS of a direction) is decided by the last bit of a library call, not by the integrator.
+#ifdef ORACLE_NUDGE_TRIG
+inline float o_cos(float x) { return std::nextafter(std::cos(x), 2.0f); }
+inline float o_sin(float x) { return std::nextafter(std::sin(x), 2.0f); }
+#else
+inline float o_cos(float x) { return std::cos(x); }
+inline float o_sin(float x) { return std::sin(x); }
+#endif
 inline float sign(float x) { return std::copysign(1.0f, x); }
 inline float fract(float x) { return x - std::floor(x); }
 inline float lerp(float a, float b, float t) { return a + t * (b - a); }

@@ -80,7 +80,7 @@ inline float2 sample_uniform_disk_concentric(float2 u_in) {// sampling.cpp:13-22
     auto p = std::abs(u.x) > std::abs(u.y);
     auto r = p ? u.x : u.y;
     auto theta = p ? pi_over_four * (u.y / u.x) : pi_over_two - pi_over_four * (u.x / u.y);
-    return {r * std::cos(theta), r * std::sin(theta)};
+    return {r * o_cos(theta), r * o_sin(theta)};
 }
 inline float3 sample_cosine_hemisphere(float2 u) {// sampling.cpp:24-31
     auto d = sample_uniform_disk_concentric(u);
@@ -95,7 +95,7 @@ inline float3 sample_uniform_sphere(float2 u) {// sampling.cpp:100-108
     auto z = 1.0f - 2.0f * u.x;
     auto r = std::sqrt(std::max(1.0f - z * z, 0.0f));
     auto phi = 2.0f * pi * u.y;
-    return {r * std::cos(phi), r * std::sin(phi), z};
+    return {r * o_cos(phi), r * o_sin(phi), z};
 }
 constexpr float uniform_sphere_pdf = inv_pi * 0.25f;// sampling.h:24
 inline float balance_heuristic(float f_pdf, float g_pdf) {// sampling.cpp:133-140,153-155

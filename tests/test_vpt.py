@@ -22,6 +22,15 @@ render {{ cameras {{ @cam }} shapes {{ @lamp{shapes} }} {env_medium}
   integrator : MegaVPTNaive {{ depth {{ 16 }} rr_depth {{ 1000 }} }} }}
 """
 
+# the absorbing box behind an (almost) index-matched smooth Glass boundary (test_medium_boundary_enter_and_exit_through_an_index_matched_box)
+BOX = """
+Surface skin : Glass { Kr : Constant { v { 1 } } Kt : Constant { v { 1 } } eta : Constant { v { 1.0001 } } }
+Shape box : InlineMesh {
+  positions { -20,-20,1, 20,-20,1, 20,20,1, -20,20,1, -20,-20,2, 20,-20,2, 20,20,2, -20,20,2 }
+  indices { 0,2,1, 0,3,2,  4,5,6, 4,6,7,  0,1,5, 0,5,4,  3,6,2, 3,7,6,  0,7,3, 0,4,7,  1,2,6, 1,6,5 }
+  surface { @skin } medium { @fog } }
+"""
+
 
 def _mean(scene, spp):
     o = Oracle(scene)
@@ -75,15 +84,8 @@ def test_vacuum_scene_matches_the_path_tracer():
 def test_medium_boundary_enter_and_exit_through_an_index_matched_box():
     """A box of absorbing medium behind an (almost) index-matched smooth Glass boundary between the camera and the lamp:
     enter -> distance sampling inside -> exit, i.e. the MediumTracker round trip; L ~ L_e * exp(-sigma_a * thickness)."""
-    box = """
-Surface skin : Glass { Kr : Constant { v { 1 } } Kt : Constant { v { 1 } } eta : Constant { v { 1.0001 } } }
-Shape box : InlineMesh {
-  positions { -20,-20,1, 20,-20,1, 20,20,1, -20,20,1, -20,-20,2, 20,-20,2, 20,20,2, -20,20,2 }
-  indices { 0,2,1, 0,3,2,  4,5,6, 4,6,7,  0,1,5, 0,5,4,  3,6,2, 3,7,6,  0,7,3, 0,4,7,  1,2,6, 1,6,5 }
-  surface { @skin } medium { @fog } }
-"""
     sigma = np.array([0.3, 0.6, 0.9])
-    sc = Scene.from_string(SLAB.format(sa=", ".join(map(str, sigma)), ss="0", g=0, prio=0, dist=4, extra=box, shapes=", @box", env_medium=""))
+    sc = Scene.from_string(SLAB.format(sa=", ".join(map(str, sigma)), ss="0", g=0, prio=0, dist=4, extra=BOX, shapes=", @box", env_medium=""))
     v = sc.view()
     assert v.medium_count == 1 and v.integrator.environment_medium_tag == 0xFFFFFFFF
     assert (v.instances[1].handle.x & 16) != 0 and (v.instances[1].handle.y >> 24) == 0  # LR_SHAPE_HAS_MEDIUM, medium tag 0
