@@ -148,7 +148,7 @@ $(LIBDIR)/liblrhip.so: $(HIP_OBJ) $(VARIANT_OBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -o $@ $^
 
 # experimental kernel builds for A/B runs on the GPU box:
-#   make hip-variant NAME=w3 DEFS="-DLR_WAVES_HEAVY=3" [VARIANT_MASKS="0 1"]
+#   make hip-variant NAME=w3 DEFS="-DLR_WAVES_LAYERED=3" [VARIANT_MASKS="0 1"]
 VOBJDIR := $(LIBDIR)/variants/obj_$(NAME)
 hip-variant:
 	@mkdir -p $(VOBJDIR)

@@ -24,7 +24,8 @@ namespace lrd {
 // stand on Disney, Plastic and Matte surfaces with two image maps each makes two lookups, not five one kind after the other.  Camera class
 // (<4116>) 1075 -> 1125 Msamples/s at 64 spp, films bit-identical; but the six registers the results wait in cost the kernels whose scenes
 // hold no image at all their allocation: C2 <4096> 1075 -> 1032, the kitchen class' wavefront passes 585 -> 577 (profiles/r06i_lobe_forms.txt).
-// So: in the lean kernels WITH the Disney closure (the variants textured scenes of the camera class' kind take), form 1 elsewhere.
+// So: in the lean kernels WITH the Disney closure (the variants textured scenes of the camera class' kind take), form 1 elsewhere
+// (kernel_forms.h: LR_LOBE_FORM).
 // Measured with it and not kept: the closure resolution as one out-of-line function with the passes inside (its 41 words of result through
 // memory, 340 scratch instructions of callee saves per call: every configuration 5 - 12 % slower, r06g), and touching the texels ahead of
 // the lookups instead of keeping results (-7 %, r06i).
@@ -32,15 +33,6 @@ namespace lrd {
 // looked-up slot (DSurface::first_lookup, asked for beside the closure record) -- three registers instead of form 2's six.  The lean passes of
 // wavefront mode: the kitchen class' floor / Oren-Nayar / plastic albedo and the bumpy plastic's normal map were four lookups one kind after
 // the other; 592 -> 607 Msamples/s at 512 spp, films bit-identical (profiles/r06q_lobe_form3.txt).
-#ifndef LR_LOBE_FORM
-#if defined(LR_VARIANT) && ((LR_VARIANT) & 16) && !((LR_VARIANT) & (96 | 256))
-#define LR_LOBE_FORM 2
-#elif defined(LR_VARIANT) && ((LR_VARIANT) & 1024) && !((LR_VARIANT) & (96 | 256))
-#define LR_LOBE_FORM 3
-#else
-#define LR_LOBE_FORM 1
-#endif
-#endif
 // closure record + shading frame of surface `t` on top of frame `base`: NormalMapWrapper (surface.h:236-254) and
 // per-hit texture resolution for "dynamic" closures (the constant ones were folded at upload by the same resolve_closure)
 LR_D void load_lobe(const LobeTables &tb, f2 uv, f3 ng, f3 wo, uint32_t t, const Frame &base, DClosure &c, Frame &fr, float eta_i = 1.f) {
@@ -53,14 +45,10 @@ LR_D void load_lobe(const LobeTables &tb, f2 uv, f3 ng, f3 wo, uint32_t t, const
         auto &rec = tb.surfaces[t];
         auto &raw = rec.raw;
 #if LR_LOBE_FORM == 3
-        // the lookup of a slot whose texture is NOT constant: the out-of-line lambda of round 3 (dev_math.h: LR_TEX_LAMBDA), now asked for
+        // the lookup of a slot whose texture is NOT constant: the out-of-line lambda of round 3 (dev_math.h: LR_TEX_LAMBDA_ATTR), now asked for
         // those slots only -- a constant slot is a plain load from the surface's own record (dev_scene.h: DSurface), independent of the
         // other slots' and issued with them, where it used to be a call and a dependent round trip through the texture table each
-#if LR_TEX_BY_VALUE
-        const auto lookup = [&](int32_t id) { return texture_eval_slot(tb.textures, tb.texels, id, uv.x, uv.y); };
-#else
         const auto lookup = [&](int32_t id) LR_TEX_LAMBDA_ATTR { return texture_eval_tables(tb.textures, tb.texels, id, uv); };
-#endif
         // ONE lookup of every lane at ONE place ahead of everything else: the lane's normal map if it has one, else its first looked-up slot.
         // (The kitchen class' lean hits: floor and Oren-Nayar albedo, the plastic's albedo, the bumpy plastic's normal map -- four lookups one
         // kind after the other become one, and the plastic's roughness.)
@@ -80,14 +68,8 @@ LR_D void load_lobe(const LobeTables &tb, f2 uv, f3 ng, f3 wo, uint32_t t, const
         }
         auto dyn = c.dynamic;
 #if LR_LOBE_FORM != 3
-        // the lookup of a slot whose texture is NOT constant: the out-of-line lambda of round 3 (dev_math.h: LR_TEX_LAMBDA), now asked for
-        // those slots only -- a constant slot is a plain load from the surface's own record (dev_scene.h: DSurface), independent of the
-        // other slots' and issued with them, where it used to be a call and a dependent round trip through the texture table each
-#if LR_TEX_BY_VALUE
-        const auto lookup = [&](int32_t id) { return texture_eval_slot(tb.textures, tb.texels, id, uv.x, uv.y); };
-#else
+        // (the lookup of a slot whose texture is not constant, as in form 3 above)
         const auto lookup = [&](int32_t id) LR_TEX_LAMBDA_ATTR { return texture_eval_tables(tb.textures, tb.texels, id, uv); };
-#endif
 #endif
         const auto mask = rec.dynamic_mask;
 #if LR_LOBE_FORM == 2

@@ -25,13 +25,7 @@ LR_HD uint32_t xxhash32_3(uint32_t x, uint32_t y, uint32_t z) {// rng.cpp:38-51
     return h ^ (h >> 16u);
 }
 
-#ifndef LR_NEST// free Mix / Layered composition: only in the variants that carry kFeatNest (512), one translation unit per variant
-#if defined(LR_VARIANT) && ((LR_VARIANT) & 512) && !((LR_VARIANT) & 256)
-#define LR_NEST 1
-#else
-#define LR_NEST 0
-#endif
-#endif
+// LR_NEST (kernel_forms.h): free Mix / Layered composition, only in the variants that carry kFeatNest (512), one translation unit per variant
 
 // Layered surfaces on a path through the interfaces (lr_scene.h: LR_LAYERED_MAX_LEVELS; a Layered surface as an interface of a Layered
 // surface needs the free-composition variants).  The functions below are templated on LV, the Layered levels still allowed INSIDE the

@@ -6,63 +6,29 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "kernel_forms.h"
 
 #define LR_HD __host__ __device__ __forceinline__
 #define LR_D __device__ __forceinline__
 // Wave votes on a BOOL (round 5).  HIP's __any / __ballot take an int: the compiler materialises the predicate in a VGPR and compares
 // it with zero again (v_cndmask_b32_e64 v, 0, 1, s[..] + v_cmp_ne_u32 s[..], 0, v -- two half-rate VALU instructions per vote, five votes
 // per iteration of the traversal loop: 42 of its ~960 issue cycles).  The ballot builtin takes the lane mask the compare already
-// produced (LR_VOTE_BUILTIN=0 restores the library forms for A/B).
-#ifndef LR_VOTE_BUILTIN
-#define LR_VOTE_BUILTIN 1
-#endif
-#if LR_VOTE_BUILTIN
+// produced.
 __device__ __forceinline__ unsigned long long lr_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 __device__ __forceinline__ bool lr_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
-#else
-__device__ __forceinline__ unsigned long long lr_ballot(bool p) { return __ballot(p); }
-__device__ __forceinline__ bool lr_any(bool p) { return __any(p) != 0; }
-#endif
 // Out-of-line device functions.  LR_HEAVY: the Disney / Mix / Layered path of the variants that hold Mix or Layered
 // (dev_heavy.h) is always a real call.  LR_CALL: the texture lookup and the environment evaluate / sample are real
 // calls only in those same variants (one copy instead of one per use: -60 % code, fewer spills in the main loop);
 // in the lean ones the call overhead costs more than it saves (measured inline vs call: C2 +2 %, C3 +1.4 %, C4 +7 %).
-// Every variant is its own translation unit (megapath_variant.hip defines LR_VARIANT), so this is a preprocessor choice.
-// LR_TEX_LAMBDA: the texture lookup behind the callback resolve_closure gets from load_lobe (dev_heavy.h; dev_shade.h: texture_eval_slot -- a
-// capturing lambda until round 6), its ~20 uses in ONE place.  In the lean
-// variants it is the one real call they make -- only hits on textured closures take it: <0> 73 -> 58 KB, <20> 220 -> 153 KB, and C2,
+// Which kernel takes which: kernel_forms.h.
+// LR_TEX_LAMBDA_ATTR: the texture lookup behind the callback resolve_closure gets from load_lobe (dev_heavy.h: `lookup`), its ~20 uses in
+// ONE place.  In the lean variants it is the one real call they make -- only hits on textured closures take it: <0> 73 -> 58 KB, <20> 220 -> 153 KB, and C2,
 // which never runs it, +1.5 % from what the rest of the kernel gets out of the smaller function (C3 / C4 unchanged; inlined at every
 // use: C4 -1.2 %; EVERY texture lookup through one out-of-line function instead: C2 the same, C3 -0.5 %, C4 -1 %;
 // profiles/archive/r03ae_texture_lambda_ab.txt).  Rounds 1-2 had the same call by accident: the inliner left the lambda out
 // of line while the texture code still held powf.
-#ifndef LR_CALL
-#if defined(LR_VARIANT) && ((LR_VARIANT) & (96 | 256)) && !defined(LR_CALL_INLINE)
-#define LR_CALL __device__ __noinline__
-#define LR_TEX_LAMBDA __device__ __forceinline__
-#else
-#define LR_CALL __device__ __forceinline__
-#define LR_TEX_LAMBDA __device__ __noinline__
-#endif
-#endif
-#ifndef LR_TEX_LAMBDA
-#define LR_TEX_LAMBDA __device__ __forceinline__// (LR_CALL given by the translation unit, heavy_variant.hip: texture_eval_tables is a real call itself)
-#endif
-#ifndef LR_TEX_BY_VALUE
-#define LR_TEX_BY_VALUE 0
-#endif
-#if defined(LR_VARIANT) && !((LR_VARIANT) & (96 | 256)) && !defined(LR_CALL_INLINE)
-#define LR_TEX_LAMBDA_ATTR __attribute__((noinline))
-#else
-#define LR_TEX_LAMBDA_ATTR
-#endif
 #ifndef LR_HEAVY
 #define LR_HEAVY __device__ __noinline__
-#endif
-
-// hit reconstruction gathers from the baked per-triangle records (dev_scene.h: DShadeTri): +2.6 % on C2;
-// -DLR_BAKED_SHADING=0 restores the instance -> triangle -> vertices chain of the reference for A/B
-#ifndef LR_BAKED_SHADING
-#define LR_BAKED_SHADING 1
 #endif
 
 namespace lrd {

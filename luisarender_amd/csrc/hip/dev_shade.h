@@ -388,14 +388,8 @@ LR_D float pow_nonpositive(float c, float g) {
 // footprint: the camera-class stand-in's eight 2k x 2k maps are 128 MB instead of 512 MB, and the frame runs 3.5-4 % faster
 // (profiles/r05zd_byte_textures.txt; profiles/r05zb_c4_texture_size.txt: the same frame with smaller images).  Which scenes get it:
 // lrhip_set_texture_storage (lrhip.h).
-// (compiled into the variants that make real calls, the heavy kernels and the lean kernels of the kFeatByteTex bit: dev_wavefront.h)
-#ifndef LR_BYTE_TEXELS
-#if defined(LR_VARIANT) && !((LR_VARIANT) & (96 | 256 | 8192))
-#define LR_BYTE_TEXELS 0
-#else
-#define LR_BYTE_TEXELS 1
-#endif
-#endif
+// (LR_BYTE_TEXELS, kernel_forms.h: compiled into the variants that make real calls, the heavy kernels and the lean kernels of the kFeatByteTex
+// bit: dev_wavefront.h)
 LR_HD float byte_over_255(float b) {// correctly rounded b / 255.f for b = 0 .. 255: one Newton step on the reciprocal product
     const auto q = b * (1.f / 255.f);
     const auto r = fmaf(-q, 255.f, b);
@@ -404,15 +398,8 @@ LR_HD float byte_over_255(float b) {// correctly rounded b / 255.f for b = 0 .. 
 // LR_TEX_WIDE_RECORD: the out-of-line lookup reads a texture's record in one round trip and everything through explicitly global loads (texture_record below).
 // Measured (profiles/r06u_texture_record_loads.txt, films bit-identical): camera class <12308> 1146 -> 1163 Msamples/s at 64 spp; the kitchen
 // class' lean wavefront passes LOSE 0.4 % (the looked-up record's 28 registers across the call: 32 -> 48 spilled VGPRs in <5128>) and keep the
-// field-by-field reads.  The lookup as a free function with its arguments by value instead of a capturing lambda (LR_TEX_BY_VALUE, dev_heavy.h):
-// camera class -2.7 %, kitchen class -1 %: not kept.
-#ifndef LR_TEX_WIDE_RECORD
-#if defined(LR_VARIANT) && ((LR_VARIANT) & 16) && !((LR_VARIANT) & (96 | 256))
-#define LR_TEX_WIDE_RECORD 1// the lean kernels with the Disney closure: what textured scenes of the camera class' kind render on
-#else
-#define LR_TEX_WIDE_RECORD 0
-#endif
-#endif
+// field-by-field reads (kernel_forms.h: LR_TEX_WIDE_RECORD).  The lookup as a free function with its arguments by value instead of a capturing
+// lambda was tried: camera class -2.7 %, kitchen class -1 %.
 // sixteen bytes from GLOBAL memory, said so
 typedef float lr_v4f __attribute__((ext_vector_type(4)));
 LR_D float4 global_load_f4(const void *base, uint64_t index) {
@@ -529,11 +516,6 @@ LR_CALL float4 texture_eval_tables(const lr_texture *textures, const float *texe
         return ti.scale[ch] * c;
     };
     return make_float4(decode(v.x, 0), decode(v.y, 1), decode(v.z, 2), 0.f);// (the fourth channel of an image: never read on the device, see texel_at)
-}
-// the lookup load_lobe makes per looked-up slot (dev_heavy.h): out of line in the lean variants too (dev_math.h: LR_TEX_LAMBDA), with its
-// arguments BY VALUE -- as a capturing lambda it read the tables' pointers and uv back from the closure object through flat loads
-LR_TEX_LAMBDA float4 texture_eval_slot(const lr_texture *textures, const float *texels, int32_t id, float u, float v) {
-    return texture_eval_tables(textures, texels, id, f2{u, v});
 }
 LR_D float4 texture_eval(const DScene &scene, int32_t id, f2 uv_it) { return texture_eval_tables(scene.textures, scene.texels, id, uv_it); }
 
@@ -974,8 +956,7 @@ LR_CALL EnvSample env_sample_one(EnvTables tb, const DEnvironment *envp, f2 u) {
 // explicit stack, in the reference's operation order (post-order: a.L * scale_a + b.L * scale_b, the pdfs interpolated), by out-of-line
 // functions that only the variants which make real calls anyway hold (lrhip_kernels.hip picks one for such a scene) -- the lean kernels' register
 // allocation never sees them.  At most LR_ENV_MAX_COMBINED_DEPTH Combined nodes on a path (lr_scene.h; checked at upload).
-#if (defined(LR_VARIANT) && ((LR_VARIANT) & (96 | 256))) || defined(LR_ENV_TREE_WALK)// (LR_ENV_TREE_WALK: lrhip_light.hip, the light queries)
-#define LR_ENV_TREE 1
+#ifdef LR_ENV_TREE// (kernel_forms.h: the kernels that make real calls, and a unit that defines LR_ENV_TREE_WALK -- lrhip_light.hip, lrhip_gather.hip)
 __device__ __noinline__ EnvEval env_evaluate_tree(EnvTables tb, const DEnvironment *root, f3 wi) {// CombinedInstance::evaluate, combined.cpp:57-78
     const DEnvironment *node[LR_ENV_MAX_COMBINED_DEPTH];
     f3 local[LR_ENV_MAX_COMBINED_DEPTH];

@@ -336,14 +336,6 @@ LR_D void trav_fetch_wait() {
 // The slab tests of one staged packet and the near -> far order of its children: key[i] = (float_bits(t_near) & ~3) | slot, ascending, a
 // missed child's key is kInvalid (negative as an int; a valid key is a non-negative float's bits).
 LR_D void trav_slab_sort_q(float4 q0, float4 q1, float4 q2, const TravState &tr, f3 inv, uint32_t (&key)[4]) {
-#ifdef LR_PROBE_NODE
-    {// sensitivity probe: LR_PROBE_NODE extra dependent VALU ops per node step
-        float dummy = tr.t_min;
-#pragma unroll
-        for (auto i = 0; i < LR_PROBE_NODE; i++) { asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(dummy)); }
-        asm volatile("" ::"v"(dummy));
-    }
-#endif
     // packet: q0 = (origin.xyz, scale.x)  q1 = (lo_x4, lo_y4, lo_z4, hi_x4) bytes
     //         q2 = (hi_y4, hi_z4, scale.y, scale.z)  q3 = child[4]
     // An EMPTY slot has inverted planes (lo 255, hi 0) and names the scene's sentinel leaf (a triangle nothing hits,
@@ -373,16 +365,13 @@ LR_D void trav_slab_sort_q(float4 q0, float4 q1, float4 q2, const TravState &tr,
         key[i] = h ? ((__float_as_uint(tn) & 0xfffffffcu) | static_cast<uint32_t>(i)) : kInvalid;
     }
     // (the slot kept in the key as a byte offset, slot * 4 in four key bits, saves the shift: measured, no change)
-    // near -> far: 5-comparator network on (float_bits(t) & ~3) | slot keys (t >= 0)
+    // near -> far: 5-comparator network on (float_bits(t) & ~3) | slot keys (t >= 0).  (Three comparators -- the nearest child first, the others as they
+    // fall -- were tried: +1.05 % steps per ray on C2 in tools/bvh_sim.cpp BVH_SIM_PARTIAL_SORT, 966 against 989 Msamples/s.)
     cswap(key[0], key[1]);
     cswap(key[2], key[3]);
     cswap(key[0], key[2]);
-#if !defined(LR_SORT_COMPARATORS) || LR_SORT_COMPARATORS >= 4// (experiment: 3 = the nearest child first, the others as they fall; tools/bvh_sim.cpp BVH_SIM_PARTIAL_SORT: +1.05 % steps per ray on C2; measured 966 against 989 Msamples/s)
     cswap(key[1], key[3]);
-#endif
-#if !defined(LR_SORT_COMPARATORS) || LR_SORT_COMPARATORS >= 5
     cswap(key[1], key[2]);
-#endif
 }
 LR_D void trav_slab_sort(const float4 *mine, const TravState &tr, f3 inv, uint32_t (&key)[4]) { trav_slab_sort_q(mine[0], mine[1], mine[2], tr, inv, key); }
 // the staged packets are read until here: no lane's next fetch may land before every lane's reads have returned
@@ -393,12 +382,9 @@ LR_D void trav_slab_sort(const float4 *mine, const TravState &tr, f3 inv, uint32
 // C2 pool kernel 1044 -> 1079 Msamples/s, C3 1026 -> 1052, films bit-identical (profiles/r05zf_setprio.txt).  On the way: the whole
 // loop at 3 over a shading block at 0: -1 %; the shading block at 3 over the loop at 0: +0.5 %; only the fetch requests at 3: +2.0 %;
 // the chain starting before the sort network, or the leaf's pop raised as well: -0.3 % each; the shading block at 1 / 2 / 3: the same.
-#ifndef LR_WAVE_PRIORITIES
-#define LR_WAVE_PRIORITIES 1
-#endif
-LR_D void prio_chain() { if (LR_WAVE_PRIORITIES) { __builtin_amdgcn_s_setprio(3); } }
-LR_D void prio_tests() { if (LR_WAVE_PRIORITIES) { __builtin_amdgcn_s_setprio(0); } }
-LR_D void prio_shade() { if (LR_WAVE_PRIORITIES) { __builtin_amdgcn_s_setprio(2); } }
+LR_D void prio_chain() { __builtin_amdgcn_s_setprio(3); }
+LR_D void prio_tests() { __builtin_amdgcn_s_setprio(0); }
+LR_D void prio_shade() { __builtin_amdgcn_s_setprio(2); }
 LR_D void trav_packets_done() {
     __builtin_amdgcn_s_waitcnt(0xc07f);// lgkmcnt(0) (vmcnt / expcnt untouched)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -430,13 +416,7 @@ LR_D void trav_packets_done() {
 //   * the hit as MOVES UNDER EXEC, pinned as ctx_start's are (one region for a closest hit's three words, one for `occluded` and the stack drop of a
 //     shadow ray: five moves, seven scalar instructions, two branches): C2 1308.1 -> 1299.2, it LOSES 0.7 %;
 //   * the step of a push as a select on the key's sign: the stride in a VGPR of its own, <4096> spills two (not run).
-#ifndef LR_STRAIGHT_TAIL
-#if defined(LR_VARIANT) && ((((LR_VARIANT) & 4096) && !((LR_VARIANT) & 2048)) || ((LR_VARIANT) & ~15) == 0)
-#define LR_STRAIGHT_TAIL 3
-#else
-#define LR_STRAIGHT_TAIL 0
-#endif
-#endif
+// (the selection rule: kernel_forms.h)
 // the pushes / pop of a node step: far -> near so that the nearest is popped first; the nearest stays in `cur`
 template<bool D, bool STRAIGHT = false>
 LR_D void trav_node_tail(const TraversalStack &stack, const TravLane &tl, TravState &tr, uint32_t &spb, const uint32_t (&key)[4], uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3) {
@@ -514,9 +494,7 @@ LR_D void trav_node_step(const TraversalStack &stack, const TravLane &tl, TravSt
         const auto r0 = ref_of(key[0]), r1 = ref_of(key[1]), r2 = ref_of(key[2]), r3 = ref_of(key[3]);
         if (deep) { trav_node_tail<true>(stack, tl, tr, spb, key, r0, r1, r2, r3); }
         else { trav_node_tail<false, STRAIGHT>(stack, tl, tr, spb, key, r0, r1, r2, r3); }
-#ifndef LR_TRACE_PROBE
         if (COUNT && key[0] == kInvalid) { stats.nodes_empty++; }
-#endif
     }
     trav_packets_done();
 }
@@ -536,13 +514,7 @@ LR_D void trav_node_step(const TraversalStack &stack, const TravLane &tl, TravSt
 // LR_LEAF_TAIL_ONE_COMPARE: what the leaf test does with a hit, written around ONE compare of the phase (pool kernels without the alpha test: three
 // VALU instructions per iteration, C2 1102 -> 1115, C3 1100 -> 1110, C4 1229 -> 1235 Msamples/s, films bit-identical; the one-path kernels gain
 // nothing and keep the round 1-5 form; the ALPHA kernels' allocation takes it badly -- <5128> 32 -> 65 spilled VGPRs: profiles/r06zq_leaf_tail.txt)
-#ifndef LR_LEAF_TAIL_ONE_COMPARE
-#if defined(LR_VARIANT) && ((LR_VARIANT) & 4096)
-#define LR_LEAF_TAIL_ONE_COMPARE 1
-#else
-#define LR_LEAF_TAIL_ONE_COMPARE 0
-#endif
-#endif
+// (the selection rule: kernel_forms.h)
 struct LeafTriangle { float4 a, b, c; };
 LR_D LeafTriangle trav_leaf_fetch(const TravLane &tl, uint32_t ref) {
     // (a 32-bit byte offset from the scalar table base: 48 B x 2^27 triangles does not fit 32 bits, 48 B x the 89 M a 4 GB table holds does -- lrhip_upload_scene refuses more)
@@ -573,14 +545,6 @@ LR_D bool trav_leaf_test(TravState &tr, uint32_t ref, const LeafTriangle &tri, T
     auto found = false;
     auto a = tri.a, b = tri.b, c = tri.c;
     if (COUNT) { stats.tris++; }
-#ifdef LR_PROBE_LEAF
-    {
-        float dummy = tr.t_min;
-#pragma unroll
-        for (auto i = 0; i < LR_PROBE_LEAF; i++) { asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(dummy)); }
-        asm volatile("" ::"v"(dummy));
-    }
-#endif
     auto flags = __float_as_uint(c.w);
     f3 p0 = mk3(a.x, a.y, a.z), e1 = mk3(b.x, b.y, b.z), e2 = mk3(c.x, c.y, c.z);
 #ifdef LR_EXACT_LEAF
@@ -622,6 +586,9 @@ LR_D bool trav_leaf_test(TravState &tr, uint32_t ref, const LeafTriangle &tri, T
     // minimum, inf - inf and 0 * inf are NaN: the determinant need not be asked.  u >= 0 && v >= 0 as ONE compare of their minimum: a NaN in one
     // of them makes v_min return the other, but then u + v is NaN and fails too.  One VALU and two scalar instructions per iteration: C2 1124 -> 1130,
     // C3 1113 -> 1119, C5 626 -> 630 Msamples/s, films bit-identical: profiles/r06zt_leaf_test_compares.txt)
+#if defined(__FINITE_MATH_ONLY__) && __FINITE_MATH_ONLY__
+#error "trav_leaf_test: the compares below reject a degenerate triangle through infinities and NaNs; build without -ffinite-math-only / -ffast-math"
+#endif
     (void)det;
     auto ok = fminf(u, v) >= 0.f && uv_sum <= 1.f && t > tr.t_min && t < tr.t_max && (flags & 1u);
     if (ALPHA && ok && (flags & 2u) == 0u) {// park the candidate: the alpha test runs outside this loop
@@ -676,7 +643,6 @@ LR_D bool trav_leaf_test(TravState &tr, uint32_t ref, const LeafTriangle &tri, T
 }
 template<bool COUNT, bool ALPHA>
 LR_D void trav_leaf_step(const TraversalStack &stack, const TravLane &tl, TravState &tr, uint32_t &spb, bool deep, TraceStats &stats) {
-    if (LR_WAVE_PRIORITIES == 2) { prio_chain(); }
     const auto tri = trav_leaf_fetch(tl, tr.cur);
     // what the lane goes on with is read from its stack while the triangle is on its way (a lane that finds an occluder, or parks a candidate
     // for its alpha test, does not take it): one LDS round trip off the iteration's critical path -- round 5: the one-path kernel +1.5 % on
@@ -701,7 +667,7 @@ LR_D void trav_leaf_step(const TraversalStack &stack, const TravLane &tl, TravSt
 // and a wave issues at most one instruction of ANY kind every ~4.5 cycles: what an iteration costs a wave is its instruction count --
 // scalar and branch instructions included -- as much as the round trips it waits for.
 //
-// THE FUSED FLOW IN TWO HALVES (LR_POOL_FUSED_FETCH, megapool_kernel.h): trav_requests sends out both gathers of an iteration -- the packets of the
+// THE FUSED FLOW IN TWO HALVES (megapool_kernel.h: THE FUSED FLOW): trav_requests sends out both gathers of an iteration -- the packets of the
 // lanes at inner nodes into the staging area, the triangles of the lanes at leaves into registers (LeafRequest) -- and trav_consume waits for them
 // once, tests the triangles, pops, and runs the node step; a lane the node step sends to a leaf tests it in the NEXT iteration.  What a lane asks
 // for is a function of its `cur` alone, so a caller may put code between the two halves that leaves alone the `cur` of every lane at a node or a
@@ -720,7 +686,7 @@ LR_D bool trav_pair_candidate(const TravLane &tl, uint32_t cur, uint32_t spb) {/
     return static_cast<int>(cur) < static_cast<int>(kCurParked) && spb > tl.s_empty && spb <= tl.s_deep + 3u * kStackStride;
 }
 template<bool COUNT, bool ALWAYS, bool PAIR = false>
-LR_D bool trav_requests(const TraversalStack &stack, const TravLane &tl, const TravState &tr, uint32_t spb, LeafRequest &rq, bool leaves, TraceStats &stats) {
+LR_D bool trav_requests(const TraversalStack &stack, const TravLane &tl, const TravState &tr, uint32_t spb, LeafRequest &rq, TraceStats &stats) {
     const auto is_inner = static_cast<int>(tr.cur) >= 0;
     if constexpr (PAIR) {
         auto top = kInvalid;
@@ -735,7 +701,7 @@ LR_D bool trav_requests(const TraversalStack &stack, const TravLane &tl, const T
         const auto any_node = ALWAYS || lr_any(tr.cur < kCurParked);
         prio_chain();
         if (any_node) { trav_node_fetch_of(stack, tl, node); }
-        if (leaves) { trav_leaf_requests(tl, tr, rq); }
+        trav_leaf_requests(tl, tr, rq);
         LR_MARK(kProbeIssue);
         (void)stats;
         return any_node;
@@ -744,7 +710,7 @@ LR_D bool trav_requests(const TraversalStack &stack, const TravLane &tl, const T
     const auto any_inner = ALWAYS || lr_any(is_inner);
     prio_chain();
     if (any_inner) { trav_node_fetch(stack, tl, tr, is_inner); }
-    if (leaves) { trav_leaf_requests(tl, tr, rq); }
+    trav_leaf_requests(tl, tr, rq);
     LR_MARK(kProbeIssue);
     (void)stats;
     return any_inner;// the packet loads went out
@@ -784,9 +750,9 @@ LR_D void trav_iteration(const TraversalStack &stack, const TravLane &tl, TravSt
     // (a lane at an inner node pushes at most three entries); if none can -- nearly always -- every push and pop of the
     // iteration is a bare LDS access instead of a compare + branch + access per entry (round 3: +1 %)
     const auto deep = lr_any(spb > tl.s_deep);
-    if (FUSED) {// (LR_POOL_FUSED_FETCH: both gathers of the iteration requested up front, one wait)
+    if (FUSED) {// (both gathers of the iteration requested up front, one wait)
         LeafRequest rq;
-        const auto any_inner = trav_requests<COUNT, false, PAIR>(stack, tl, tr, spb, rq, true, stats);
+        const auto any_inner = trav_requests<COUNT, false, PAIR>(stack, tl, tr, spb, rq, stats);
         trav_consume<COUNT, ALPHA, PAIR>(stack, tl, tr, spb, inv, rq, any_inner, deep, stats);
         return;
     }
@@ -846,23 +812,8 @@ LR_D void trace_steps(const DScene &scene, const TraversalStack &stack, TravStat
         if (idle == ~0ull || __popcll(idle & fresh) >= refill) { return; }
     }
     for (;;) {
-#ifdef LR_TRACE_PROBE// (section cycles of the loop in the counting build: node step -> nodes_empty, end of iteration -> trace_steps_starved; lane 0 reports)
-        if (COUNT) { stats.steps++, stats.steps_busy += tr.phase != kPhaseIdle ? 1u : 0u; }
-        const auto probe_t0 = __builtin_readcyclecounter();
-#else
         if (COUNT) { stats.steps++, stats.steps_busy += tr.phase != kPhaseIdle ? 1u : 0u, stats.steps_starved += idle_at_entry ? 1u : 0u; }
-#endif
         trav_iteration<COUNT, ALPHA>(stack, tl, tr, spb, inv, stats);
-#ifdef LR_TRACE_PROBE
-        const auto probe_t1 = __builtin_readcyclecounter();
-#endif
-#ifdef LR_TRACE_PROBE
-        const auto probe_t2 = __builtin_readcyclecounter();
-        if (COUNT && (threadIdx.x & 63u) == 0u) {
-            stats.nodes_empty += static_cast<uint32_t>(probe_t1 - probe_t0);
-            stats.steps_starved += static_cast<uint32_t>(__builtin_readcyclecounter() - probe_t2);
-        }
-#endif
         if (ALPHA && alpha_tests_due(tr.phase, tr.cur)) { break; }
         // ---- ray finished: switch from the shadow ray to the closest-hit ray, or go idle.  (Nothing the tests below look at changes
         // in an iteration in which no ray ended.)

@@ -43,6 +43,21 @@ enum : uint32_t {
     kFeatGather = 131072u,
     kFeatSceneMask = kFeatEnv | kFeatAlpha | kFeatDisney | kFeatMix | kFeatLayered
 };
+// kernel_forms.h writes the bits its rules ask as preprocessor numbers
+static_assert(LR_FEAT_COUNT == kFeatCount, "kernel_forms.h: LR_FEAT_COUNT");
+static_assert(LR_FEAT_GENERIC == kFeatGeneric, "kernel_forms.h: LR_FEAT_GENERIC");
+static_assert(LR_FEAT_ENV == kFeatEnv, "kernel_forms.h: LR_FEAT_ENV");
+static_assert(LR_FEAT_ALPHA == kFeatAlpha, "kernel_forms.h: LR_FEAT_ALPHA");
+static_assert(LR_FEAT_DISNEY == kFeatDisney, "kernel_forms.h: LR_FEAT_DISNEY");
+static_assert(LR_FEAT_MIX == kFeatMix, "kernel_forms.h: LR_FEAT_MIX");
+static_assert(LR_FEAT_LAYERED == kFeatLayered, "kernel_forms.h: LR_FEAT_LAYERED");
+static_assert(LR_FEAT_VPT == kFeatVpt, "kernel_forms.h: LR_FEAT_VPT");
+static_assert(LR_FEAT_NEST == kFeatNest, "kernel_forms.h: LR_FEAT_NEST");
+static_assert(LR_FEAT_WF == kFeatWf, "kernel_forms.h: LR_FEAT_WF");
+static_assert(LR_FEAT_CONT == kFeatCont, "kernel_forms.h: LR_FEAT_CONT");
+static_assert(LR_FEAT_POOL == kFeatPool, "kernel_forms.h: LR_FEAT_POOL");
+static_assert(LR_FEAT_BYTE_TEX == kFeatByteTex, "kernel_forms.h: LR_FEAT_BYTE_TEX");
+static_assert(LR_FEAT_PADDED == kFeatPadded, "kernel_forms.h: LR_FEAT_PADDED");
 
 // ColorFilmInstance::_accumulate (color.cpp:107-130, effective_spp = 1) into the wave's LDS copy of its tile.
 LR_D void film_accumulate(float4 *pixel, f3 rgb, float clamp) {

@@ -77,13 +77,17 @@ int kernel_blocks(lrhip_ctx *ctx, const KernelEntry &entry, unsigned lds_bytes, 
 
 namespace {
 
-// the kernels that are not lean: out-of-line closures (Mix, Layered: real calls), the sibling integrators and the volumetric kernel
-constexpr uint32_t kHeavyClosureBits = lrd::kFeatMix | lrd::kFeatLayered;
+// Which code forms a kernel of a mask holds -- out-of-line closures, real calls, the decode of packed 8-bit texels -- is kernel_forms.h's to say
+// (lrd::forms: the rules the kernels themselves are compiled by).  The sibling integrators and the volumetric kernel are a selection concept:
 constexpr uint32_t kSiblingBits = lrd::kFeatAux | lrd::kFeatVpt;
-constexpr uint32_t kCallBits = kHeavyClosureBits | kSiblingBits;
-// only a kernel that decodes packed 8-bit texels will do for a scene that holds them: the lean ones of the kFeatByteTex bit, and every
-// variant that makes real calls (dev_wavefront.h)
-constexpr bool decodes_byte_texels(uint32_t mask) { return (mask & (lrd::kFeatByteTex | kCallBits)) != 0u; }
+// (a sibling integrator's kernel is never lean: the device's rule for "makes real calls" does not ask kFeatAux, the search below relies on it)
+constexpr bool siblings_make_calls() {
+    for (auto v : lrd::kSceneVariants) {
+        if ((v & kSiblingBits) != 0u && !lrd::forms::makes_calls(v)) { return false; }
+    }
+    return true;
+}
+static_assert(siblings_make_calls(), "lrd::kSceneVariants: a kFeatAux / kFeatVpt feature set without Mix, Layered or the volumetric kernel");
 
 // smallest precompiled superset of the scene's feature bits among the feature sets of one scheduler (lrd::kSceneVariants, first superset wins):
 // `pool` = the path-pool kernels of round 4 (megapool_kernel.h), otherwise the one-path-per-lane kernels.  `byte_texels`: see above; a scene
@@ -91,7 +95,7 @@ constexpr bool decodes_byte_texels(uint32_t mask) { return (mask & (lrd::kFeatBy
 uint32_t pick_scene_variant(uint32_t scene_features, bool pool, bool byte_texels) {
     for (auto v : lrd::kSceneVariants) {
         if (((v & lrd::kFeatPool) != 0u) != pool) { continue; }
-        if (byte_texels ? !decodes_byte_texels(v) : (v & lrd::kFeatByteTex) != 0u) { continue; }
+        if (byte_texels ? !lrd::forms::decodes_byte_texels(v) : (v & lrd::kFeatByteTex) != 0u) { continue; }
         if ((v & scene_features) == scene_features) { return v; }
     }
     return kNoKernel;
@@ -119,6 +123,7 @@ KernelPlan plan_kernels(const PlanInputs &in) {
     const auto sibling = (features & kSiblingBits) != 0u;
     // nested Combined environments are walked by out-of-line code (dev_shade.h: LR_ENV_TREE), which the variants that make real calls
     // anyway hold -- the ones with the Mix interpreter (the auxiliary and volumetric kernels are such variants already)
+    static_assert(lrd::forms::walks_env_tree(lrd::kFeatMix), "kernel_forms.h: a kernel with the Mix interpreter walks nested environments");
     if (in.env_tree && !sibling) { features |= lrd::kFeatMix; }
     const auto plain = pick_scene_variant(features, false, in.byte_texels);
     if (plain == kNoKernel) { return plan; }
@@ -127,7 +132,7 @@ KernelPlan plan_kernels(const PlanInputs &in) {
     // out-of-line closures: Mix / Layered surfaces, and Disney together with an alpha test (no lean <Alpha | Disney> variant is
     // precompiled; such a scene ran at 433 Msamples/s on <60> where its Mix-holding sibling ran at 480 in wavefront mode).
     // (it needs the film's fixed-point sums: a frame they cannot hold -- fixed_point_bits -- takes the float-accumulating kernels)
-    if (in.fixed_fits && in.wf_mode != 1u && in.force_features == 0u && !in.env_tree && !sibling && (plain & kHeavyClosureBits) != 0u) {
+    if (in.fixed_fits && in.wf_mode != 1u && in.force_features == 0u && !in.env_tree && !sibling && lrd::forms::holds_heavy_closures(plain)) {
         // kernels: the lean camera pass + continuation pass with the scene's environment / alpha needs, the heavy kernel with its nesting
         // (the alpha-tested traversal only where a surface may be non-opaque: the kitchen stand-in with its lace made opaque runs at 530.6
         // instead of 520.5 Msamples/s on the lean kernels without it, profiles/archive/r03ar_wavefront_without_alpha_ab.txt)
@@ -143,7 +148,7 @@ KernelPlan plan_kernels(const PlanInputs &in) {
     } else {
         // round 4: the path-pool scheduler where a pool kernel is compiled for a scene the search gives a lean kernel (no out-of-line
         // closures, no sibling integrator), and the fixed-point film can hold the frame
-        if (in.wants_pool && in.fixed_fits && in.max_depth < 65536u && (plain & kCallBits) == 0u) {
+        if (in.wants_pool && in.fixed_fits && in.max_depth < 65536u && !lrd::forms::makes_calls(plain)) {
             const auto pooled = pick_scene_variant(features, true, in.byte_texels);
             pool = pooled != kNoKernel && (pooled & lrd::kFeatWf) == 0u && find_kernel(pooled | twin) != nullptr;
             if (pool) { plan.main = pooled | twin; }
@@ -187,7 +192,7 @@ extern "C" int lrhip_plan_kernels(uint32_t features, uint32_t force_features, ui
     for (auto k = 0u; k < lrd::kWfKinds; k++) { out[3u + k] = plan.heavy[k]; }
     out[6] = plan.fixed_point ? 1u : 0u;
     const auto megapath = (features & (kSiblingBits | lrd::kFeatAov)) == 0u;
-    const auto packs = scene_kernels_decode_byte_texels((features & lrd::kFeatAlpha) != 0u, (features & kHeavyClosureBits) != 0u, in.env_tree, megapath);
+    const auto packs = scene_kernels_decode_byte_texels((features & lrd::kFeatAlpha) != 0u, lrd::forms::holds_heavy_closures(features), in.env_tree, megapath);
     out[7] = packs ? 1u : 0u;
     auto compiled = plan.family != LRHIP_FAMILY_NONE;
     for (auto mask : {plan.main, plan.cont}) { compiled = compiled && (mask == kNoKernel || find_kernel(mask) != nullptr); }

@@ -229,13 +229,8 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                 const auto ready = tr.phase == kPhaseIdle && traced_closest;
                 auto heavy_hit = false;
                 if (ready && tr.hit.inst != kInvalid) {
-#if LR_BAKED_SHADING
                     const auto rec = reinterpret_cast<const float4 *>(scene.shade_tris + tr.hit.tri);
                     const auto flags = __float_as_uint(rec[0].w), tags = __float_as_uint(rec[1].w);
-#else
-                    const auto h = reinterpret_cast<const uint4 *>(scene.instances + tr.hit.inst)[0];
-                    const auto flags = h.x & 1023u, tags = h.y;
-#endif
                     heavy_hit = (flags & LR_SHAPE_HAS_SURFACE) != 0u && scene.closures[(tags >> 12u) & 4095u].kind >= LR_SURFACE_DISNEY;
                 }
                 const auto heavy_lanes = __popcll(lr_ballot(heavy_hit));
@@ -257,14 +252,6 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                 if (traced_closest) {// one iteration of the reference's depth loop, mega_path.cpp:63-154
                     traced_closest = false;
                     if (COUNT) { local.shade_busy++; }
-#ifdef LR_PROBE_SHADE
-                    {// sensitivity probe: LR_PROBE_SHADE extra dependent VALU ops per shaded vertex
-                        float dummy = pdf_bsdf;
-#pragma unroll
-                        for (auto i = 0; i < LR_PROBE_SHADE; i++) { asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(dummy)); }
-                        asm volatile("" ::"v"(dummy));
-                    }
-#endif
                     auto wo = -tr.d;
                     auto hit = tr.hit;
                     auto hit_valid = hit.inst != kInvalid;
@@ -288,11 +275,7 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                     SurfacePoint it;
                     auto has_surface = false;
                     if (hit_valid) {
-#if LR_BAKED_SHADING
                         reconstruct_baked(scene, hit.tri, hit.u, hit.v, it);
-#else
-                        reconstruct<true>(scene, hit.inst, hit.prim, mk3(1.f - hit.u - hit.v, hit.u, hit.v), it);
-#endif
                         it.back_facing = dot(wo, it.ng) < 0.0f;
                         if (COUNT) { local.surface_hits++; }
                         if (AOV && depth == 0u) {// the first hit's buffers, aov.cpp:263-270 (the interaction's shading normal, not the closure's)
@@ -334,13 +317,8 @@ __global__ __launch_bounds__(kBlockThreads, min_waves_of(F)) void megapath_kerne
                     // radiance so far (the emission of this vertex included), sampler position -- goes into the queue of its
                     // closure kind; heavy_kernel.h shades the vertex and hands the path back as a continuation record.
                     if (WF && has_surface) {
-#if LR_BAKED_SHADING
                         const auto heavy_kind = (it.flags >> 10u) & 3u;// (baked into the triangle's record: lrhip_tables.hip, build_shade_tris)
                         if (heavy_kind != 0u) { park_kind = heavy_kind - 1u, has_surface = false; }
-#else
-                        const auto kind = scene.closures[(it.tags >> 12u) & 4095u].kind;
-                        if (kind >= LR_SURFACE_DISNEY) { park_kind = kind - LR_SURFACE_DISNEY, has_surface = false; }
-#endif
                     }
                     if (has_surface) {
                         if (COUNT) { local.path_length_sum++, local.nee_samples++; }

@@ -57,7 +57,6 @@ namespace lrd {
 #ifndef LR_MIN_WAVES
 #define LR_MIN_WAVES 4
 #endif
-// -DLR_POOL_SINGLE: the lane's second context never takes a path (a diagnostic: this kernel's machinery under the round 1-3 scheduling)
 #ifndef LR_POOL_SHADE_LANES
 #define LR_POOL_SHADE_LANES 56// lanes with a context to shade that end the traversal loop
 #endif
@@ -72,33 +71,23 @@ namespace lrd {
 // 8 in four A/Bs (r05a, r05d, r05l, r05r), 6 and 4 behind.
 #define LR_POOL_TURNOVER_LANES 12
 #endif
-#ifndef LR_POOL_PARK_ON_STACK
-#define LR_POOL_PARK_ON_STACK 1// the five parked words of the ray in flight go on top of the lane's traversal stack (0: an LDS area of their own, LR_STACK_LDS <= 11)
-#endif
-#ifndef LR_POOL_FUSED_FETCH
-// The pool kernels request BOTH gathers of an iteration -- the packets of the lanes at inner nodes, the triangles of the lanes at leaves -- up
-// front and wait once (dev_trace.h: trav_iteration<.., FUSED>); a lane the node step sends to a leaf tests it in the next iteration (5 %
-// more iterations, each with one round trip instead of two in a row).  Round 4 measured this at +-1 % and left it off; with the loop a
+// THE FUSED FLOW.  The pool kernels request BOTH gathers of an iteration -- the packets of the lanes at inner nodes, the triangles of the lanes at
+// leaves -- up front and wait once (dev_trace.h: trav_iteration<.., FUSED>; FUSED in pool_trace); a lane the node step sends to a leaf tests it in
+// the next iteration (5 % more iterations, each with one round trip instead of two in a row).  Round 4 measured this at +-1 % and left it off; with the loop a
 // fifth lighter the round trips weigh more: C2 1022.5 -> 1043.2 at 1024 spp, C3 1024.6 -> 1033.3, C4 1015.4 -> 1031.4,
 // films BIT-IDENTICAL (both flows share trav_leaf_test; profiles/r05o_pool_fused_fetch.txt).  The one-path-per-lane kernels keep the serial
 // flow: their scenes' walks are a handful of steps out of the L1, and the extra iterations cost the Cornell box 7 %.  So do the ALPHA pool
 // kernels (alpha-tested traversal): fused, the alpha-only stand-in runs at 750 instead of 859 Msamples/s and C5 at 504 instead of 567
 // (profiles/r05q_fused_fetch_alpha_kernels.txt); the wavefront passes WITHOUT alpha gain 0.7 %.
-#define LR_POOL_FUSED_FETCH 1
-#endif
-#ifndef LR_POOL_FUSED_ALPHA
-#define LR_POOL_FUSED_ALPHA 0// (the ALPHA pool kernels under the fused flow: see above)
-#endif
 #ifndef LR_POOL_EARLY_FETCH
 // EARLY FETCH (fused flow only).  The end of an iteration -- the votes on ended rays, the turnover of LR_POOL_TURNOVER_LANES of them (19 v_swap_b32,
 // ctx_start, three v_rcp), the exit tests -- used to stand between the node step and the next iteration's requests, with nothing of the wave in
 // flight.  It changes nothing that the requests read: 1 = pool_trace sends an iteration's requests (dev_trace.h: trav_requests) right behind the
-// node step of the one before and runs the tail while they are on their way; 2 = only the four packet loads go early, the leaf lanes' triangles are
-// requested behind the tail (their twelve registers are not live across it); 0 = the round 5-6 order.  See pool_trace for why the requested packets
-// are the right ones.  Same instructions, same order of every lane's arithmetic: films and counters are bit-identical (tests/test_gpu_early_fetch.py).
+// node step of the one before and runs the tail while they are on their way; 0 = the round 5-6 order (`make noearly`).  See pool_trace for why the
+// requested packets are the right ones.  Same instructions, same order of every lane's arithmetic: films and counters are bit-identical (tests/test_gpu_early_fetch.py).
 // Against the commit before, same box, runs alternating (profiles/early_fetch_ab_c2.txt): C2 1132.6 -> 1188.3 Msamples/s (+4.9 %, the runs of a side
-// 0.06 % apart), C3 1125 -> 1173, C4 1262 -> 1295, C2 under PaddedSobol 1039 -> 1086; 2 (packets only): 1149; the loop's census 426 -> 421 instructions,
-// 246 VALU on both sides, <4096> still at 128 VGPRs without a spill.
+// 0.06 % apart), C3 1125 -> 1173, C4 1262 -> 1295, C2 under PaddedSobol 1039 -> 1086; with only the four packet loads early and
+// the leaf lanes' triangles requested behind the tail: C2 1149; the loop's census 426 -> 421 instructions, 246 VALU on both sides, <4096> still at 128 VGPRs without a spill.
 #define LR_POOL_EARLY_FETCH 1
 #endif
 #ifndef LR_POOL_LEAF_NODE_PAIR
@@ -112,15 +101,6 @@ namespace lrd {
 // (+ 2.15 %, the runs of a side 0.06 - 0.18 % apart); <4096> still at 128 VGPRs without a spill.  The loop is issue-bound: the first form, + 33 instructions
 // per iteration (a per-lane select of the packet, a vote on a compound predicate), saved the same iterations and gained nothing -- 1194.6 against 1195.3.
 #define LR_POOL_LEAF_NODE_PAIR 1
-#endif
-#ifndef LR_POOL_EARLY_TAIL_PRIO
-#define LR_POOL_EARLY_TAIL_PRIO 3// the tail behind the early requests stays at the chain's priority (dev_trace.h: WAVE PRIORITIES); 0: it runs at the tests' priority (C2 1188 -> 1178)
-#endif
-#ifndef LR_POOL_STATE_LEAN
-#define LR_POOL_STATE_LEAN 1
-#endif
-#ifndef LR_POOL_RAY_INIT
-#define LR_POOL_RAY_INIT if (!mine)
 #endif
 #ifndef LR_POOL_SHADOW_RIDE
 // SHADOW RIDE (every pool kernel but the wavefront passes).  A path's last vertex spawns no closest-hit ray, and where it has a light sample the context
@@ -231,13 +211,9 @@ LR_D void ctx_swap(PathCtx &a, PathCtx &b) {
 // The exchange at a TURNOVER inside the traversal loop (pool_trace): `a` has just completed its job, `b` waits with rays.  Of the context that leaves
 // only what the shading block reads of a traced job is live -- the segment (no, nd), the hit (tri, u, v; read only if the job held a closest-hit ray,
 // and written where that ray ends), the flags -- and the hit of the one that arrives is dead: twelve of the nineteen words are copies under the same
-// EXEC, not exchanges.  C2 1190.1 -> 1197.9 Msamples/s (+0.65 %, a side's runs 0.02 % apart), films bit-identical (profiles/early_fetch_full_line.txt);
-// 0 restores the nineteen v_swap_b32.
-#ifndef LR_POOL_TURNOVER_MOVES
-#define LR_POOL_TURNOVER_MOVES 1
-#endif
+// EXEC, not exchanges.  Against nineteen v_swap_b32: C2 1190.1 -> 1197.9 Msamples/s (+0.65 %, a side's runs 0.02 % apart), films bit-identical
+// (profiles/early_fetch_full_line.txt).
 LR_D void ctx_turnover(PathCtx &a, PathCtx &b) {
-    if (LR_POOL_TURNOVER_MOVES == 0) { ctx_swap(a, b); return; }
     a.so = b.so, a.sd = b.sd, a.s_tmax = b.s_tmax, a.n_tmin = b.n_tmin, a.n_tmax = b.n_tmax;
     b.tri = a.tri, b.u = a.u, b.v = a.v;
     swap_words(a.no.x, b.no.x), swap_words(a.no.y, b.no.y), swap_words(a.no.z, b.no.z);
@@ -252,9 +228,6 @@ LR_D uint32_t lane_rank(unsigned long long mask) {// lanes of `mask` below this 
 constexpr uint32_t kCtxRays = kCtxShadow | kCtxClosest;
 // flags of a context that the shading block has work for: a traced job, or (while the launch has samples left) no path at all
 LR_D bool ctx_shadeable(uint32_t flags, bool samples_left) {
-#ifdef LR_POOL_SINGLE// (experiment: the second context never takes a path -- the round 1-3 scheduling in this kernel's clothes)
-    if ((flags & kCtxSide) != 0u) { samples_left = false; }
-#endif
     return (flags & kCtxDone) != 0u || (samples_left && (flags & kCtxOpen) == 0u);
 }
 // whether the shading block is due: enough lanes hold a context for it, or enough of them have nothing left to trace, or nothing is in
@@ -278,8 +251,8 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
     auto spb = tl.spb_of(tr.sp);
     if (tr.phase == kPhaseIdle) { tr.cur = kCurIdle; }// (inside the loop a lane's state is read off `cur`: dev_trace.h, TravLane)
     auto for_alpha = false;// (ALPHA: the wave leaves for the alpha tests of its parked candidates and comes straight back)
-    constexpr bool FUSED = LR_POOL_FUSED_FETCH != 0 && (!ALPHA || LR_POOL_FUSED_ALPHA != 0);
-    constexpr int EARLY = FUSED ? LR_POOL_EARLY_FETCH : 0;
+    constexpr bool FUSED = !ALPHA;// (the alpha pool kernels keep the serial flow: THE FUSED FLOW above)
+    constexpr bool EARLY = FUSED && LR_POOL_EARLY_FETCH != 0;
     constexpr bool PAIR = FUSED && LR_POOL_LEAF_NODE_PAIR != 0;
 #ifdef LR_STALL_PROBE
     if (COUNT) { probe_start(stats); }
@@ -298,22 +271,17 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
     // the tail and compare -- which lanes pair, and with which node -- and trav_consume compares the node a paired lane pops with the one it asked for.
     LeafRequest rq;
     [[maybe_unused]] auto asked = tr.cur;// (counting kernels: what the lane's requests were made for)
-    if (EARLY != 0) { trav_requests<COUNT, true, PAIR>(stack, tl, tr, spb, rq, EARLY == 1, stats); }
+    if (EARLY) { trav_requests<COUNT, true, PAIR>(stack, tl, tr, spb, rq, stats); }
     for (;;) {
         LR_MARK(kProbeTail, tr.cur);// (dev_trace.h, THE STALL PROBE: what the end of the previous iteration took)
         if (COUNT) {
             stats.steps++, stats.steps_busy += tr.phase != kPhaseIdle ? 1u : 0u;
-#ifndef LR_TRACE_PROBE
             stats.steps_starved += tr.phase == kPhaseIdle && ((cur.flags | oth.flags) & kCtxOpen) == 0u ? 1u : 0u;// no path left to hold
-#endif
         }
-#ifdef LR_TRACE_PROBE// (section cycles of the loop in the counting build: the iteration's walk -> nodes_empty, end of iteration -> trace_steps_starved; lane 0 reports)
-        const auto probe_t0 = __builtin_readcyclecounter();
-#endif
-        if (EARLY != 0) {
+        if (EARLY) {
             if (COUNT) {
                 const auto same = tr.cur == asked || (asked == kInvalid && (tr.cur == 0u || tr.cur == kCurIdle));
-                const auto leaf = EARLY != 1 || rq.at_leaf == (static_cast<int>(tr.cur) < static_cast<int>(kCurParked));// (the triangle on its way is a leaf lane's)
+                const auto leaf = rq.at_leaf == (static_cast<int>(tr.cur) < static_cast<int>(kCurParked));// (the triangle on its way is a leaf lane's)
                 stats.early_fetch_broken += same && leaf ? 0u : 1u;
                 if (PAIR) {
                     auto pair = false;
@@ -322,30 +290,18 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
                     stats.early_fetch_broken += pair == rq.pair && (!pair || top == rq.pair_node) ? 0u : 1u;
                 }
             }
-            if (EARLY == 2) { trav_leaf_requests(tl, tr, rq); }
             const auto any_inner = PAIR || lr_any(static_cast<int>(tr.cur) >= 0), deep = lr_any(spb > tl.s_deep);// (from the lanes' state BEHIND the tail; PAIR: a leaf lane may join the node step -- no vote: a wave in this loop all but always has a lane for it, and a node step without one is a skipped branch)
             trav_consume<COUNT, ALPHA, PAIR>(stack, tl, tr, spb, inv, rq, any_inner, deep, stats);
-            trav_requests<COUNT, true, PAIR>(stack, tl, tr, spb, rq, EARLY == 1, stats);
-            if (LR_POOL_EARLY_TAIL_PRIO == 0) { prio_tests(); }
+            trav_requests<COUNT, true, PAIR>(stack, tl, tr, spb, rq, stats);// (the tail below stays at the chain's priority; at the tests': C2 1188 -> 1178)
             if (COUNT) { asked = tr.cur; }
         } else {
             trav_iteration<COUNT, ALPHA, FUSED, PAIR>(stack, tl, tr, spb, inv, stats);
         }
-#ifdef LR_TRACE_PROBE
-        const auto probe_t1 = __builtin_readcyclecounter();
-        const auto probe_t2 = probe_t1;
-#endif
         if (ALPHA && alpha_tests_due(tr.phase, tr.cur)) { for_alpha = true; break; }
         // ---- rays that ended: the job's next ray, the other context's job, or idle -- once LR_POOL_TURNOVER_LANES lanes wait with one, or no
         // lane has anything left to traverse.  (Nothing below changes in an iteration without a turnover: the exit tests run behind one.)
         const auto ended = tr.cur == kInvalid;
         const auto n_ended = static_cast<uint32_t>(__popcll(lr_ballot(ended)));
-#ifdef LR_TRACE_PROBE
-        if (COUNT && (threadIdx.x & 63u) == 0u) {
-            stats.nodes_empty += static_cast<uint32_t>(probe_t1 - probe_t0);
-            stats.steps_starved += static_cast<uint32_t>(__builtin_readcyclecounter() - probe_t2);
-        }
-#endif
         if (n_ended == 0u) { continue; }
         if (n_ended < static_cast<uint32_t>(LR_POOL_TURNOVER_LANES) && lr_any(tr.cur < kCurParked)) { continue; }
         if (ended) {
@@ -372,7 +328,7 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
     }
     // EARLY: the wave leaves with requests in flight -- packets on their way into the staging area, which the shading block is about to use for
     // parking.  They are waited for here, once per call, and dropped: the next call asks again (one request in ~25 iterations is wasted).
-    if (EARLY != 0) { trav_fetch_wait(); }
+    if (EARLY) { trav_fetch_wait(); }
     LR_MARK(kProbeTail, tr.cur);
     prio_shade();
     tr.sp = tl.sp_of(spb);
@@ -381,11 +337,8 @@ LR_D bool pool_trace(const DScene &scene, const TraversalStack &stack, TravState
 
 // PADDED kernels: a stretch of a vertex's draws -- one number, two numbers, and a fourth where `four` -- is ONE real call, so that the hashes' and the
 // permutation's temporaries are not the shading block's: <20482> 16 -> 7 spilled VGPRs, C2 under PaddedSobol 974 -> 1004 Msamples/s at 256 spp, the
-// camera class 1067 -> 1111, films bit-identical (profiles/r06za_padded_draws_out_of_line.txt; LR_PADDED_DRAWS_OUT_OF_LINE=0 restores the inline draws).
+// camera class 1067 -> 1111 against the inline draws, films bit-identical (profiles/r06za_padded_draws_out_of_line.txt).
 // The same for the run-time generic sampler (state in; numbers and state out: eight return registers): Sobol 886 -> 880, PCG32 980 -> 968 -- not kept.
-#ifndef LR_PADDED_DRAWS_OUT_OF_LINE
-#define LR_PADDED_DRAWS_OUT_OF_LINE 1
-#endif
 struct PaddedDraws {
     float a, b, c, d;
 };
@@ -406,13 +359,7 @@ struct PaddedDraws {
 // closure: their shading block is the one that spills (<12308> 67 -> 44 VGPRs), and the call's temporaries are not its allocation's any more.
 // Camera class 1166 -> 1227 Msamples/s at 64 spp, films bit-identical; the kernels without Disney LOSE (bedroom class <4100> 1092 -> 1015, 12 -> 27
 // spilled; the kitchen class' wavefront passes 640 -> 627) and keep the inline form (profiles/r06zd_light_sample_out_of_line.txt).
-#ifndef LR_LIGHT_OUT_OF_LINE
-#if defined(LR_VARIANT) && ((LR_VARIANT) & 16) && !((LR_VARIANT) & (96 | 256))
-#define LR_LIGHT_OUT_OF_LINE 1
-#else
-#define LR_LIGHT_OUT_OF_LINE 0
-#endif
-#endif
+// (the selection rule: kernel_forms.h)
 template<bool ENV>
 [[maybe_unused]] static __device__ __noinline__ LightPick sample_one_light_call(const DScene *scene, f3 p, f3 ng, f3 ns, uint32_t offset_bits, float u0, float u1, float u2) {
     SurfacePoint it{};
@@ -503,11 +450,6 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
     constexpr bool STASH_SCALAR_ITEM = STASH && !ENV;
     __shared__ uint32_t s_stack[kStackLds * kBlockThreads];
     __shared__ float4 s_stage[kWavesPerBlock * kStageWave];// 4 KiB of node packets per wave
-#if LR_POOL_PARK_ON_STACK == 0
-    // what a lane keeps of its ray in flight across the shading block: five words, [word][thread] (the LDS an 11-entry stack leaves, see below)
-    __shared__ uint32_t s_park[5u * kBlockThreads];
-    static_assert(kStackLds + 5u <= 16u, "the parking area is carved out of the round 1-3 stack: compile such pool variants with LR_STACK_LDS <= 11");
-#endif
     __shared__ unsigned long long s_film[CONT ? 1u : kWavesPerBlock * 192u];// per-wave tile accumulators, fixed point [pixel][rgb]
 #ifdef LR_STALL_PROBE
     __shared__ uint32_t s_probe[kWavesPerBlock * kProbeWords];
@@ -610,11 +552,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
             // offers its current one
             if (tr.phase == kPhaseIdle && !ctx_shadeable(oth.flags, samples_left)) { ctx_swap(cur, oth); }
             // (a context that waits with the rays of its job is none of the shading block's business)
-#ifdef LR_POOL_SINGLE
-            const auto mine = (oth.flags & kCtxDone) != 0u || ((oth.flags & kCtxOpen) == 0u && (oth.flags & kCtxSide) == 0u);
-#else
             const auto mine = (oth.flags & kCtxDone) != 0u || (oth.flags & kCtxOpen) == 0u;
-#endif
             // ---- Of the lane's two contexts the shading block needs the traced segment and the hit of the one it shades, and it
             // produces that context's next rays in `shadow` / `ray` (which start as the rays the context holds: where it is not `mine`
             // they come out as they went in).  Everything else must leave the registers the shading block is allocated in (314 spilled
@@ -630,24 +568,15 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                 // one word of small things (traversal phase 0-2, occluded 3, stack depth 5-11, flags of the current context 12-19, of the
                 // other one 20-27).  With these six in registers the block spills 37 VGPRs on its hot path, without them 12 off it (round 4,
                 // the measurement behind section 4.1c of DESIGN.md): they are the difference between a traversal loop with and without its
-                // L1.  One goes into the spare word of the staging area, five into the LDS the pool kernels' stack gives up (11 entries
-                // per lane instead of 16).
+                // L1.  One goes into the spare word of the staging area, five ...
                 const auto keep_word = (tr.phase & 7u) | (tr.occluded ? 8u : 0u) | (tr.sp << 5u) | (cur.flags << 12u) | (oth.flags << 20u);
                 stage[192u + lane] = make_float4(cur.nd.x, cur.nd.y, cur.nd.z, __uint_as_float(keep_word));
-#if LR_POOL_PARK_ON_STACK// ... on top of the lane's own traversal stack (the entries above sp; beyond the LDS part: the overflow area in HBM)
+                // ... on top of the lane's own traversal stack (the entries above sp; beyond the LDS part: the overflow area in HBM)
                 stack.push(tr.sp + 0u, tr.phase != kPhaseIdle ? tr.hit.tri : cur.tri);
                 stack.push(tr.sp + 1u, __float_as_uint(tr.phase != kPhaseIdle ? tr.hit.u : cur.u));
                 stack.push(tr.sp + 2u, __float_as_uint(tr.phase != kPhaseIdle ? tr.hit.v : cur.v));
                 stack.push(tr.sp + 3u, __float_as_uint(tr.t_max));
                 stack.push(tr.sp + 4u, tr.cur);
-#else
-                const auto park = s_park + tid;
-                park[0u * kBlockThreads] = tr.phase != kPhaseIdle ? tr.hit.tri : cur.tri;
-                park[1u * kBlockThreads] = __float_as_uint(tr.phase != kPhaseIdle ? tr.hit.u : cur.u);
-                park[2u * kBlockThreads] = __float_as_uint(tr.phase != kPhaseIdle ? tr.hit.v : cur.v);
-                park[3u * kBlockThreads] = __float_as_uint(tr.t_max);
-                park[4u * kBlockThreads] = tr.cur;
-#endif
                 asm volatile("" ::: "memory");// (the values must not be forwarded to the loads at the end of the block: they are to LEAVE the registers)
             }
             // ==== LR_POOL_PATH_STASH, the fill: the stash holds fewer started paths than this batch has lanes that shade, and the launch has samples
@@ -687,7 +616,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
             // ---- the context's path
             PathSampler<PCG> sampler{};
             Ray ray{}, shadow{};
-            LR_POOL_RAY_INIT {
+            if (!mine) {
                 shadow.o = oth.so, shadow.d = oth.sd, shadow.t_min = 0.f, shadow.t_max = oth.s_tmax;
                 ray.o = oth.no, ray.d = oth.nd, ray.t_min = oth.n_tmin, ray.t_max = oth.n_tmax;
             }
@@ -703,10 +632,9 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
             const auto hit_u = oth.u, hit_v = oth.v;
             // What the block reads of the record, and when (round 5).  Quads 0-2 -- NEE term, pdf, throughput, depth, radiance, sampler word 0
             // -- where the context's path is taken up.  Quad 3's pixel and work item never change along a path: written when the path starts,
-            // read where it ends or is parked (LR_POOL_STATE_LEAN: +1.7 % on C2; 0 restores the read at every vertex).  The GENERIC sampler's
+            // read where it ends or is parked (against a read at every vertex: +1.7 % on C2).  The GENERIC sampler's
             // other three words (quads 3 and 4) are read where the vertex's random numbers are drawn and written back right there: outside
             // that stretch the sampler holds no register (sampler_take / sampler_leave below).
-            constexpr bool LEAN_STATE = LR_POOL_STATE_LEAN != 0;
             auto word0 = 0u;// the sampler's first state word (Independent: its only one)
             const auto load_ids = [&]() {
                 const auto q3 = state_load(side, 3u);
@@ -747,7 +675,6 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                 dp = packed & (RIDE ? 0x7fffffu : 0x3fffffu);
                 Li = mk3(q2.x, q2.y, q2.z);
                 word0 = __float_as_uint(q2.w);
-                if (!LEAN_STATE) { load_ids(); }
                 if (!PCG) {
                     uint32_t words[kWfSamplerWordsMax] = {word0, 0u, 0u, 0u};
                     sampler.restore(scene, words);
@@ -839,7 +766,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                                 const auto leader = __ffsll(static_cast<long long>(mask)) - 1;
                                 const auto out = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(reserved), leader)) + lane_rank(mask);
                                 if (park_kind == k && out < scene.wf.capacity) {// (capacity >= the slice's paths: never full; a bound, not a policy)
-                                    if (LEAN_STATE) { load_ids(); }
+                                    load_ids();
                                     if (PCG) { sampler_take(0u); }
                                     const auto q = wf_heavy_queue<SAMPLER_WORDS>(scene, k);
                                     q.put3(out, 0u, rd);
@@ -863,7 +790,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                         if (COUNT) { local.path_length_sum++, local.nee_samples++; }
                         // random numbers are drawn where they are used, in the reference's order (mega_path.cpp:90-97):
                         // light selection, light surface (2), lobe, bsdf (2), [rr]
-                        if constexpr (PADDED && LR_PADDED_DRAWS_OUT_OF_LINE != 0) {
+                        if constexpr (PADDED) {
                             sampler_take(0u);
                             const auto r = padded_draws(&scene, sampler.lo, sampler.w3, sampler.w2, false);
                             u_light_selection = r.a, u_light_surface = f2{r.b, r.c};
@@ -909,7 +836,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                         const auto t_e1 = probe_clock();
                         t_eval = t_e1 - t_l1;
 #endif
-                        if constexpr (PADDED && LR_PADDED_DRAWS_OUT_OF_LINE != 0) {
+                        if constexpr (PADDED) {
                             sampler_take(1u);
                             const auto r = padded_draws(&scene, sampler.lo, sampler.w3, sampler.w2, rr);
                             u_lobe = r.a, u_bsdf = f2{r.b, r.c}, u_rr = r.d;
@@ -959,7 +886,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                 if (park_kind != kInvalid) { path_open = false; }// (it goes on elsewhere: nothing to accumulate here)
             }
             if (path_open && !want_shadow && !want_closest) {// path complete: film.accumulate (integrator.cpp:74)
-                if (LEAN_STATE) { load_ids(); }
+                load_ids();
                 LR_POOL_FILM_ADD(Li, pixel_index, path_item, dp >> 16u);
                 path_open = false;
             }
@@ -987,7 +914,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                         got = true, need = false;
                         sampler_left = false;// (the context takes another path: every quad of its record is written below)
                         if (final_shadow) {// the ids of the path that ends leave for the extra quad
-                            if (LEAN_STATE) { load_ids(); }
+                            load_ids();
                             state_store(side, QUADS, make_float4(__uint_as_float(pixel_index), __uint_as_float(path_item), __uint_as_float(dp >> 16u), 0.f));
                         }
                         pixel_index = __float_as_uint(e2.y);
@@ -1032,7 +959,7 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                     path_open = true;
                 } else {// MegakernelPathTracingInstance::Li prologue, mega_path.cpp:52-62
                     if (final_shadow) {// the ids of the path that ends leave for the extra quad here: nothing of it is alive across the camera code
-                        if (LEAN_STATE) { load_ids(); }
+                        load_ids();
                         state_store(side, QUADS, make_float4(__uint_as_float(pixel_index), __uint_as_float(path_item), __uint_as_float(dp >> 16u), 0.f));
                     }
                     pixel_index = new_py * scene.camera.width + new_px;
@@ -1068,8 +995,6 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                     } else if (got) {
                         state_store(side, 3u, make_float4(__uint_as_float(pixel_index), __uint_as_float(path_item), __uint_as_float(words[1]), __uint_as_float(words[2])));
                         if (PCG) { state_store(side, QUADS - 1u, make_float4(__uint_as_float(words[3]), 0.f, 0.f, 0.f)); }
-                    } else if (!LEAN_STATE && !PCG) {
-                        state_store(side, 3u, make_float4(__uint_as_float(pixel_index), __uint_as_float(path_item), 0.f, 0.f));
                     }
                 }
                 if (COUNT) { local.closest_rays += want_closest ? 1u : 0u, local.shadow_rays += want_shadow ? 1u : 0u; }
@@ -1087,16 +1012,9 @@ __global__ __launch_bounds__(kBlockThreads, LR_MIN_WAVES) void megapool_kernel(D
                 const auto keep_word = __float_as_uint(p3.w);
                 tr.phase = keep_word & 7u, tr.occluded = (keep_word & 8u) != 0u;
                 tr.sp = (keep_word >> 5u) & 127u;
-#if LR_POOL_PARK_ON_STACK
                 const auto keep_tri = stack.pop(tr.sp + 0u);
                 const auto keep_u = __uint_as_float(stack.pop(tr.sp + 1u)), keep_v = __uint_as_float(stack.pop(tr.sp + 2u));
                 tr.t_max = __uint_as_float(stack.pop(tr.sp + 3u)), tr.cur = stack.pop(tr.sp + 4u);
-#else
-                const auto park = s_park + tid;
-                const auto keep_tri = park[0u * kBlockThreads];
-                const auto keep_u = __uint_as_float(park[1u * kBlockThreads]), keep_v = __uint_as_float(park[2u * kBlockThreads]);
-                tr.t_max = __uint_as_float(park[3u * kBlockThreads]), tr.cur = park[4u * kBlockThreads];
-#endif
                 cur.flags = (keep_word >> 12u) & 0xffu, cur.tri = keep_tri, cur.u = keep_u, cur.v = keep_v;
                 tr.hit.tri = keep_tri, tr.hit.u = keep_u, tr.hit.v = keep_v;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
