@@ -31,8 +31,8 @@ HOST_HDR := $(wildcard $(HOSTDIR)/*.h) $(wildcard include/*.h)
 HIP_SRC := $(wildcard $(HIPDIR)/lrhip_*.hip)
 HIP_HDR := $(wildcard $(HIPDIR)/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip oracle oracle-ulp cli clean hip-variant variant-lib ref ieee shallow noearly nopair noride nostash nostraight
-all: host oracle hip cli ieee shallow noearly nopair noride nostash nostraight
+.PHONY: all host hip oracle oracle-ulp cli clean hip-variant variant-lib ref ieee shallow noearly nopair noride nostash nostraight nolightrec
+all: host oracle hip cli ieee shallow noearly nopair noride nostash nostraight nolightrec
 
 # oracle/_ref: the reference's OWN sources compiled in place against the scalar LuisaCompute stand-in of oracle/ref_shim
 # (test infrastructure: pins oracle/ to the reference; needs /root/reference, so only where the reference tree exists)
@@ -214,6 +214,15 @@ $(LIBDIR)/variants/liblrhip_nostash.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hi
 nostraight: $(LIBDIR)/variants/liblrhip_nostraight.so
 $(LIBDIR)/variants/liblrhip_nostraight.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
 	$(MAKE) --no-print-directory hip-variant NAME=nostraight DEFS='-DLR_STRAIGHT_TAIL=0' VARIANT_MASKS='0 1 4096 4097 4098 4099 4100 4101 4102 4103 4116 4117 20482 20483 12308 12309' HEAVY_MASKS=
+
+# Kernels once more WITHOUT the light sample's records (dev_shade.h: LR_LIGHT_RECORDS): a light sample walks light instance -> instance -> alias
+# entry -> triangle indices -> three vertices and computes the emissive triangle's normal and area per sample.  The lean one-path kernels <0> - <3> (of them <2> and <3> take the
+# records in the shipped library, kernel_forms.h) and the masks of `noride`.  TEST INFRASTRUCTURE: the records hold what that code computes, from the same function
+# (dev_shade.h: triangle_constants), so the shipped library's frames, its counters and its light queries must equal this library's
+# (tests/test_gpu_light_records.py).
+nolightrec: $(LIBDIR)/variants/liblrhip_nolightrec.so
+$(LIBDIR)/variants/liblrhip_nolightrec.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
+	$(MAKE) --no-print-directory hip-variant NAME=nolightrec DEFS='-DLR_LIGHT_RECORDS=0' VARIANT_MASKS='0 1 2 3 4096 4097 4098 4099 4100 4101 4102 4103 4116 4117 20482 20483 12308 12309' HEAVY_MASKS=
 
 cli: $(BINDIR)/luisa-render-cli
 $(BINDIR)/luisa-render-cli: $(HOSTDIR)/cli.cpp $(HOSTDIR)/plugin_megapath.cpp $(LIBDIR)/liblrhost.so $(HOST_HDR)

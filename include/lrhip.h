@@ -907,13 +907,18 @@ int lrhip_plan_kernels(uint32_t features, uint32_t force_features, uint32_t flag
  * as lrhip_upload_scene / lrhip_update_scene / lrhip_set_instance_transforms / lrhip_set_mesh_vertices left them, copied to `out`.
  * Synchronises.  The tables: the 64-byte BVH packets; the 48-byte baked triangles and, behind the last one, the all-zero sentinel the empty
  * node slots name; the 128-byte instance records; the 128-byte shading records; and, as table 8, the object-space vertex table of 32-byte
- * lr_vertex records that lrhip_set_mesh_vertices writes (ids 4 to 7 name no table).  LRHIP_ERROR_INVALID before any upload, for an unknown
- * table and for a range that is not inside the table.                                                                                  */
+ * lr_vertex records that lrhip_set_mesh_vertices writes (ids 4 to 7 name no table).  Tables 16 and 17 are the light sample's records, built
+ * on the device: 96 bytes per light instance (its instance id, the base and length of its alias table, its first triangle record; the shape's
+ * property flags, tags and offset bits; the four columns of object_to_world, a quad each) and 80 bytes per (light instance, primitive)
+ * (object-space p0 p1 p2 with the world-space geometric normal in the quads' fourth words; uv0 uv1; uv2, world-space area, pdf table entry).
+ * LRHIP_ERROR_INVALID before any upload, for an unknown table and for a range that is not inside the table.                              */
 #define LRHIP_TABLE_NODES 0u
 #define LRHIP_TABLE_BVH_TRIANGLES 1u
 #define LRHIP_TABLE_INSTANCES 2u
 #define LRHIP_TABLE_SHADE_TRIANGLES 3u
 #define LRHIP_TABLE_VERTICES 8u
+#define LRHIP_TABLE_LIGHT_INSTANCES 16u
+#define LRHIP_TABLE_LIGHT_TRIANGLES 17u
 int lrhip_read_scene_table(lrhip_ctx *ctx, uint32_t which, uint64_t byte_offset, uint64_t bytes, void *out);
 /* size in bytes of that table in the uploaded scene (0: none, or an unknown table) */
 uint64_t lrhip_scene_table_bytes(lrhip_ctx *ctx, uint32_t which);

@@ -131,6 +131,32 @@ struct DShadeTri {// 8 x float4
 };
 static_assert(sizeof(DShadeTri) == 128, "one line per triangle");
 
+// Light sampling reads two records of its own (dev_shade.h: LR_LIGHT_RECORDS; built ON THE DEVICE, light_record_kernels.h): what
+// _sample_area (uniform.cpp:107-123) gathered per sample through light instance -> instance -> alias entry -> triangle indices -> three
+// vertices, five dependent round trips, is three: this record, the alias entry (beside lights[tag]), the triangle's record.
+// One light instance: where its tables are, the handle words a sampled point carries, and the object-to-world columns of its instance --
+// the sample never touches `instances`.
+struct alignas(16) DLightInstance {
+    uint32_t instance_id, alias_base, alias_count, tri_base;// instance | its mesh's slice of tri_alias, handle.z | its first DLightTri
+    uint32_t flags, tags, offset_bits, pad;                 // handle.x & 1023, handle.y, handle.w
+    float c0[3]; uint32_t pad0;
+    float c1[3]; uint32_t pad1;
+    float c2[3]; uint32_t pad2;
+    float t[3];  uint32_t pad3;
+};
+static_assert(sizeof(DLightInstance) == 96, "DLightInstance: six quads");
+// One (light instance, primitive): the constants of the emissive triangle until its instance moves or its mesh is deformed.  The vertices stay
+// in OBJECT space -- the sampled point is M (b0 p0 + b1 p1 + b2 p2) + t as before -- ng and area are the world-space ones, exactly as
+// reconstruct<false> computes them (dev_shade.h: triangle_constants, the one piece of source of both).
+struct alignas(16) DLightTri {
+    float p0[3]; float ng_x;
+    float p1[3]; float ng_y;
+    float p2[3]; float ng_z;
+    float uv0[2], uv1[2];
+    float uv2[2]; float area, tri_pdf;
+};
+static_assert(sizeof(DLightTri) == 80, "DLightTri: five quads");
+
 // ---- wavefront mode (round 3): scenes with Mix / Layered surfaces.  The out-of-line closures do not live in the megakernel any
 // more: a LEAN megakernel (kFeatWf variants) PARKS a path that hits a Disney / Mix / Layered surface -- its state goes into a queue
 // in HBM, one queue per closure kind, and the lane takes the next sample -- a separate kernel (heavy_kernel.h) shades the parked
@@ -213,6 +239,12 @@ struct DScene {
     float *aov_partial;
     uint32_t aov_channels;
     uint32_t aov_offset[LR_AOV_COMPONENTS];
+    // the light sample's records (appended, so no other field moves): [light_instance_count] and one DLightTri per (light instance, primitive)
+    // (light_tris_exact: the same table baked by a unit that is built without contraction and with correctly rounded division and square
+    // root, for the kernels that are built that way; kernel_forms.h: LR_LIGHT_TRIS)
+    const DLightInstance *light_records;
+    const DLightTri *light_tris;
+    const DLightTri *light_tris_exact;
 };
 
 // The scene record reaches the kernels through a pointer into constant memory, not by value: as a 400-byte kernel argument

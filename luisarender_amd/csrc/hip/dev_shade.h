@@ -654,6 +654,27 @@ LR_D float intersection_offset_factor(uint32_t handle_w) {// shape.cpp:88-93
     return clampf(x * 255.f + 1.f, 1.f, 256.f);
 }
 
+// The lines of Geometry::shading_point (geometry.cpp:345-389) that do not depend on where in the triangle the point lies: the object-space
+// vertices and uvs as the vertex quads hold them, the edges, and the world-space geometric normal and area under the columns m0 m1 m2 of the
+// instance's object-to-world matrix.  ONE piece of source for reconstruct<> below, which evaluates it per point, and for the kernel that
+// bakes it once per emissive triangle (light_record_kernels.h): same expressions, same order.
+struct TriangleConstants {
+    f3 p0, p1, p2, dp0, dp1, ng;
+    f2 uv0, uv1, uv2;
+    float area;
+};
+LR_D TriangleConstants triangle_constants(f3 m0, f3 m1, f3 m2, float4 a0, float4 a1, float4 b0, float4 b1, float4 c0, float4 c1) {
+    TriangleConstants k;
+    auto mul = [&](f3 v) { return m0 * v.x + m1 * v.y + m2 * v.z; };
+    k.p0 = mk3(a0.x, a0.y, a0.z), k.p1 = mk3(b0.x, b0.y, b0.z), k.p2 = mk3(c0.x, c0.y, c0.z);
+    k.uv0 = f2{a1.z, a1.w}, k.uv1 = f2{b1.z, b1.w}, k.uv2 = f2{c1.z, c1.w};
+    k.dp0 = k.p1 - k.p0, k.dp1 = k.p2 - k.p0;
+    auto c = cross(mul(k.dp0), mul(k.dp1));
+    k.area = length(c) * .5f;
+    k.ng = normalize(c);
+    return k;
+}
+
 // Geometry::shading_point, geometry.cpp:345-389.  FULL = false computes only what a sampled light
 // point needs (p, ng, area, uv) with the same arithmetic.
 template<bool FULL>
@@ -670,12 +691,13 @@ LR_D void reconstruct(const DScene &scene, uint32_t inst_id, uint32_t prim, f3 b
     f3 m0 = mk3(q0.x, q0.y, q0.z), m1 = mk3(q1.x, q1.y, q1.z), m2 = mk3(q2.x, q2.y, q2.z), mt = mk3(q3.x, q3.y, q3.z);
     auto mul = [&](f3 v) { return m0 * v.x + m1 * v.y + m2 * v.z; };
     f3 p0 = mk3(a0.x, a0.y, a0.z), p1 = mk3(b0.x, b0.y, b0.z), p2 = mk3(c0.x, c0.y, c0.z);
-    f2 uv0{a1.z, a1.w}, uv1{b1.z, b1.w}, uv2{c1.z, c1.w};
-    auto dp0 = p1 - p0, dp1 = p2 - p0;
     sp.p = mul(bary.x * p0 + bary.y * p1 + bary.z * p2) + mt;
-    auto c = cross(mul(dp0), mul(dp1));
-    sp.area = length(c) * .5f;
-    sp.ng = normalize(c);
+    // (behind the point, where these lines stood: the kernels that keep this form keep their instruction order)
+    const auto k = triangle_constants(m0, m1, m2, a0, a1, b0, b1, c0, c1);
+    const auto dp0 = k.dp0, dp1 = k.dp1;
+    const auto uv0 = k.uv0, uv1 = k.uv1, uv2 = k.uv2;
+    sp.area = k.area;
+    sp.ng = k.ng;
     sp.flags = h.x & 1023u;
     sp.tags = h.y;
     sp.offset_bits = h.w;
@@ -1122,6 +1144,44 @@ LR_D LightPick sample_one_light(const DScene &scene, const SurfacePoint &it, flo
         out.shadow.d = wi;
         out.shadow.t_min = 0.f, out.shadow.t_max = kFloatMax;
     } else {// _sample_area, uniform.cpp:107-123
+#if LR_LIGHT_RECORDS
+        // Three round trips: the light instance's record; its alias entry (lights[tag] is known from the record's tags and can be asked for
+        // beside it); the picked triangle's record.  The point is M (b0 p0 + b1 p1 + b2 p2) + t on the object-space vertices, the expression
+        // of reconstruct<false> on its operands; ng, area, the uvs and the triangle's pdf are the record's, baked by triangle_constants.
+        // The chain below is five dependent round trips, 6 900 of a C2 batch's 43 500 cycles by the stall probe.  Against the parent commit: C2
+        // 1334.1 -> 1349.6 Msamples/s (+1.16 %), PaddedSobol-C2 +1.4 %, C3 / C4 inside their spreads, films bit-identical (profiles/light_records_ab.txt).
+        auto rec = reinterpret_cast<const float4 *>(scene.light_records + tag);
+        auto h0 = reinterpret_cast<const uint4 *>(rec)[0], h1 = reinterpret_cast<const uint4 *>(rec)[1];
+        auto q0 = rec[2], q1 = rec[3], q2 = rec[4], q3 = rec[5];
+        float u_remapped;
+        auto slot = alias_slot(u_light_surface.x, h0.z, u_remapped);
+        auto entry = scene.tri_alias[h0.y + slot];
+        auto pick = alias_pick(entry.prob, entry.alias, slot, u_remapped);
+        // (MEASURED, NOT KEPT: the four columns requested behind the pick, beside the triangle's record, to free sixteen registers across the
+        // pick -- the kernels below that spill more on the records spill as much either way, profiles/light_records_ab.txt section 3)
+        f2 ut{pick.u, u_light_surface.y};// sample_uniform_triangle, sampling.cpp:89-98
+        f2 uvt = ut.x < ut.y ? f2{0.5f * ut.x, -0.5f * ut.x + ut.y} : f2{-0.5f * ut.y + ut.x, 0.5f * ut.y};
+        auto bary = mk3(uvt.x, uvt.y, 1.0f - uvt.x - uvt.y);
+        auto t = reinterpret_cast<const float4 *>(scene.LR_LIGHT_TRIS + (h0.w + pick.index));
+        auto t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4];
+        f3 m0 = mk3(q0.x, q0.y, q0.z), m1 = mk3(q1.x, q1.y, q1.z), m2 = mk3(q2.x, q2.y, q2.z), mt = mk3(q3.x, q3.y, q3.z);
+        auto mul = [&](f3 v) { return m0 * v.x + m1 * v.y + m2 * v.z; };
+        f3 p0 = mk3(t0.x, t0.y, t0.z), p1 = mk3(t1.x, t1.y, t1.z), p2 = mk3(t2.x, t2.y, t2.z);
+        f2 uv0{t3.x, t3.y}, uv1{t3.z, t3.w}, uv2{t4.x, t4.y};
+        SurfacePoint lp;
+        lp.p = mul(bary.x * p0 + bary.y * p1 + bary.z * p2) + mt;
+        lp.area = t4.z;
+        lp.ng = mk3(t0.w, t1.w, t2.w);
+        lp.flags = h1.x;
+        lp.tags = h1.y;
+        lp.offset_bits = h1.z;
+        lp.tri_offset = h0.y;
+        lp.uv = (lp.flags & LR_SHAPE_HAS_VERTEX_UV) ?
+                    f2{bary.x * uv0.x + bary.y * uv1.x + bary.z * uv2.x, bary.x * uv0.y + bary.y * uv1.y + bary.z * uv2.y} :
+                    f2{bary.y, bary.z};
+        lp.back_facing = dot(lp.ng, it.p - lp.p) < 0.f;
+        light_evaluate_with(scene, lp, t4.w, it.p, out.L, out.pdf);
+#else
         auto handle = scene.light_instances[tag];
         auto lh = reinterpret_cast<const uint4 *>(scene.instances + handle.instance_id)[0];
         auto l_tri_offset = scene.instances[handle.instance_id].triangle_offset;
@@ -1135,6 +1195,7 @@ LR_D LightPick sample_one_light(const DScene &scene, const SurfacePoint &it, flo
         reconstruct<false>(scene, handle.instance_id, pick.index, mk3(uvt.x, uvt.y, 1.0f - uvt.x - uvt.y), lp);
         lp.back_facing = dot(lp.ng, it.p - lp.p) < 0.f;
         light_evaluate(scene, lp, pick.index, it.p, out.L, out.pdf);
+#endif
         out.pdf *= prob;
         auto p_from = NULL_SHAPE ? it.p : robust_origin(it, lp.p - it.p);// spawn_ray_to, interaction.cpp:25-30
         auto Lv = lp.p - p_from;

@@ -58,6 +58,7 @@ static_assert(LR_FEAT_CONT == kFeatCont, "kernel_forms.h: LR_FEAT_CONT");
 static_assert(LR_FEAT_POOL == kFeatPool, "kernel_forms.h: LR_FEAT_POOL");
 static_assert(LR_FEAT_BYTE_TEX == kFeatByteTex, "kernel_forms.h: LR_FEAT_BYTE_TEX");
 static_assert(LR_FEAT_PADDED == kFeatPadded, "kernel_forms.h: LR_FEAT_PADDED");
+static_assert(LR_FEAT_GATHER == kFeatGather, "kernel_forms.h: LR_FEAT_GATHER");
 
 // ColorFilmInstance::_accumulate (color.cpp:107-130, effective_spp = 1) into the wave's LDS copy of its tile.
 LR_D void film_accumulate(float4 *pixel, f3 rgb, float clamp) {

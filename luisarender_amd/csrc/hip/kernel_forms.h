@@ -23,6 +23,7 @@
 #define LR_FEAT_POOL 4096
 #define LR_FEAT_BYTE_TEX 8192
 #define LR_FEAT_PADDED 16384
+#define LR_FEAT_GATHER 131072
 
 // ---- groups of kernels, as predicates of a mask M (numbers only: good in #if and in constant expressions alike)
 // the Mix / Layered interpreters: out-of-line closures (dev_heavy.h)
@@ -37,7 +38,20 @@
 #define LR_MASK_NESTED_CLOSURES(M) ((((M) & LR_FEAT_NEST) != 0) && ((M) & LR_FEAT_VPT) == 0)
 #define LR_MASK_POOL(M) (((M) & LR_FEAT_POOL) != 0)
 #define LR_MASK_POOL_WITHOUT_CONT(M) (LR_MASK_POOL(M) && ((M) & LR_FEAT_CONT) == 0)     // every pool kernel but the continuation passes
-#define LR_MASK_LEAN_ONE_PATH(M) (((M) & ~(LR_FEAT_COUNT | LR_FEAT_GENERIC | LR_FEAT_ENV | LR_FEAT_ALPHA)) == 0)// the one-path kernels of masks 0 - 15
+// built with the library's own arithmetic (Makefile: HIPFLAGS): every kernel but the volumetric and the gather kernels (variant_flags)
+#define LR_MASK_LIBRARY_ARITHMETIC(M) (((M) & (LR_FEAT_VPT | LR_FEAT_GATHER)) == 0)
+// a kernel or its counting twin, by number: the sets that a measurement names kernel by kernel
+#define LR_MASK_OR_TWIN(M, K) (((M) & ~LR_FEAT_COUNT) == (K))
+// spill more VGPRs with the light sample's records than without (profiles/light_records_ab.txt, section 3)
+#define LR_MASK_KEEPS_LIGHT_GATHERS(M)                                                                                                           \
+    (LR_MASK_OR_TWIN(M, 0) || LR_MASK_OR_TWIN(M, 4) || LR_MASK_OR_TWIN(M, 6) || LR_MASK_OR_TWIN(M, 12) || LR_MASK_OR_TWIN(M, 258) ||             \
+     LR_MASK_OR_TWIN(M, 1028) ||                                                                                                                 \
+     LR_MASK_OR_TWIN(M, 1036) || LR_MASK_OR_TWIN(M, 1038) || LR_MASK_OR_TWIN(M, 3074) || LR_MASK_OR_TWIN(M, 3084) || LR_MASK_OR_TWIN(M, 4110) || \
+     LR_MASK_OR_TWIN(M, 4112) || LR_MASK_OR_TWIN(M, 4114) || LR_MASK_OR_TWIN(M, 4116) || LR_MASK_OR_TWIN(M, 5128) || LR_MASK_OR_TWIN(M, 5132) || \
+     LR_MASK_OR_TWIN(M, 8210) || LR_MASK_OR_TWIN(M, 20486) || LR_MASK_OR_TWIN(M, 20490) || LR_MASK_OR_TWIN(M, 20498) ||                          \
+     LR_MASK_OR_TWIN(M, 28690) || LR_MASK_OR_TWIN(M, 28694) || LR_MASK_OR_TWIN(M, 32894) || LR_MASK_OR_TWIN(M, 196732) ||                        \
+     LR_MASK_OR_TWIN(M, 197244))
+#define LR_MASK_LEAN_ONE_PATH(M)(((M) & ~(LR_FEAT_COUNT | LR_FEAT_GENERIC | LR_FEAT_ENV | LR_FEAT_ALPHA)) == 0)// the one-path kernels of masks 0 - 15
 
 // LR_IS(group): whether this translation unit's kernel is of the group
 #ifdef LR_VARIANT
@@ -108,6 +122,27 @@
 #ifndef LR_LEAF_TAIL_ONE_COMPARE
 #define LR_LEAF_TAIL_ONE_COMPARE LR_DEFAULT_LEAF_TAIL_ONE_COMPARE
 #endif
+// LR_LIGHT_RECORDS: the light sample reads the light instance's and the emissive triangle's baked records in every kernel that samples a
+// light -- megakernel variants, heavy kernels, the light and gather query units (dev_shade.h: sample_one_light; profiles/light_records_ab.txt)
+// -- but the megakernel variants whose code object came out with MORE spilled VGPRs on the records than on the chain of gathers: they keep
+// the chain, each with its counting twin, and their code objects are what they were (the table: section 3 of that file).
+// 0 everywhere: `make nolightrec`
+#define LR_DEFAULT_LIGHT_RECORDS (LR_IS(LR_MASK_KEEPS_LIGHT_GATHERS) ? 0 : 1)
+#ifndef LR_LIGHT_RECORDS
+#define LR_LIGHT_RECORDS LR_DEFAULT_LIGHT_RECORDS
+#endif
+// LR_LIGHT_TRIS: WHICH table of triangle records.  A record's ng and area must be the bits the reading kernel computed per sample, so there is
+// one table per arithmetic the library is built with (Makefile): light_tris, baked by lrhip_tables.hip under HIPFLAGS, for everything built
+// with those; light_tris_exact, baked by lrhip_instance_update.hip -- no contraction, correctly rounded division and square root -- for the
+// volumetric and the gather kernels (variant_flags) and for a unit that says it is built that way (LR_EXACT_ARITHMETIC_UNIT: lrhip_light.hip,
+// lrhip_gather.hip)
+#ifndef LR_LIGHT_TRIS
+#if defined(LR_EXACT_ARITHMETIC_UNIT) || (defined(LR_VARIANT) && !LR_IS(LR_MASK_LIBRARY_ARITHMETIC))
+#define LR_LIGHT_TRIS light_tris_exact
+#else
+#define LR_LIGHT_TRIS light_tris
+#endif
+#endif
 
 // ---- the same rules for the host, of any mask
 namespace lrd::forms {
@@ -122,4 +157,6 @@ constexpr bool walks_env_tree(uint32_t m) { return makes_calls(m); }
 constexpr bool nests_closures(uint32_t m) { return LR_MASK_NESTED_CLOSURES(m); }
 constexpr int straight_tail(uint32_t m) { return LR_MASK_POOL_WITHOUT_CONT(m) || LR_MASK_LEAN_ONE_PATH(m) ? 3 : 0; }
 constexpr bool leaf_tail_one_compare(uint32_t m) { return LR_MASK_POOL(m); }
+constexpr bool light_records(uint32_t m) { return !(LR_MASK_KEEPS_LIGHT_GATHERS(m)); }
+constexpr bool exact_light_triangles(uint32_t m) { return !(LR_MASK_LIBRARY_ARITHMETIC(m)); }
 }// namespace lrd::forms

@@ -31,6 +31,7 @@ void release_scene(lrhip_ctx *ctx) {
     for (auto &b : ctx->mesh_adjacency) { b.release(); }
     ctx->mesh_adjacency.clear(), ctx->meshes.clear(), ctx->mesh_light.clear(), ctx->instance_handles.clear();
     ctx->surface_meshes_ready = false;
+    ctx->light_tri_owner = nullptr, ctx->light_record_count = 0u, ctx->light_tri_count = 0u;
     // the queues of wavefront mode and the pool kernels' state records are sized for the scene (and the memory free at the time): a new
     // scene starts without them (76-89 GB kept until lrhip_destroy starved later allocations on the same GPU)
     ctx->wf_heavy.release(), ctx->wf_cont.release(), ctx->pool.release();

@@ -6,6 +6,7 @@
 // its caller, and these are held to the light and BSDF queries' bit for bit
 #define LR_CALL __device__ __noinline__
 #define LR_ENV_TREE_WALK 1
+#define LR_EXACT_ARITHMETIC_UNIT 1// (Makefile: this unit's flags; kernel_forms.h: LR_LIGHT_TRIS)
 #include "lrhip_internal.h"
 #include "gather_kernel.h"
 

@@ -15,7 +15,21 @@ static_assert(offsetof(lrd::DInstance, c0) == 16u && offsetof(lrd::DInstance, ve
     && offsetof(lrd::DInstance, t) == 64u && offsetof(lrd::DInstance, n0) == 80u, "instance_triangle_kernel reads an instance record by quads");
 static_assert(offsetof(lrd::DShadeTri, n0) == 48u && offsetof(lrd::DShadeTri, uv1y) == 96u, "the first six quads of a shading record move");
 
+namespace lrd {
+// the light sample's triangle records with THIS unit's arithmetic (light_record_kernels.h; kernel_forms.h: LR_LIGHT_TRIS): what the kernels
+// built without contraction and with correctly rounded division and square root compute per sample
+__global__ void __launch_bounds__(kLightRecordBlock) light_triangle_record_exact_kernel(LightRecordArgs a) {
+    light_triangle_record(a, blockIdx.x * kLightRecordBlock + threadIdx.x);
+}
+}// namespace lrd
+
 namespace lrh {
+
+hipError_t launch_light_triangles_exact(lrhip_ctx *ctx, const lrd::LightRecordArgs &args) {
+    hipLaunchKernelGGL(lrd::light_triangle_record_exact_kernel, dim3((args.tri_count + lrd::kLightRecordBlock - 1u) / lrd::kLightRecordBlock),
+                       dim3(lrd::kLightRecordBlock), 0, ctx->stream, args);
+    return hipGetLastError();
+}
 
 namespace {
 
@@ -28,6 +42,8 @@ size_t table_bytes(const lrhip_ctx *ctx, uint32_t which, const void **base) {
         case LRHIP_TABLE_INSTANCES: *base = d.instances; return static_cast<size_t>(ctx->update_counts[2]) * sizeof(lrd::DInstance);
         case LRHIP_TABLE_SHADE_TRIANGLES: *base = d.shade_tris; return static_cast<size_t>(ctx->update_counts[1]) * sizeof(lrd::DShadeTri);
         case LRHIP_TABLE_VERTICES: *base = d.vertices; return static_cast<size_t>(ctx->vertex_count) * sizeof(lr_vertex);
+        case LRHIP_TABLE_LIGHT_INSTANCES: *base = d.light_records; return static_cast<size_t>(ctx->light_record_count) * sizeof(lrd::DLightInstance);
+        case LRHIP_TABLE_LIGHT_TRIANGLES: *base = d.light_tris; return static_cast<size_t>(ctx->light_tri_count) * sizeof(lrd::DLightTri);
         default: return 0u;
     }
 }
@@ -88,6 +104,9 @@ int rebake_and_refit(lrhip_ctx *ctx) {
         hipLaunchKernelGGL(lrd::instance_triangle_kernel, dim3(blocks_for(a.triangle_count)), block, 0, ctx->stream, a);
         LR_HIP_CHECK(hipGetLastError());
     }
+    // the light sample's records of the marked instances (lrhip_tables.hip: bake_light_records); an instance without a light has none, and
+    // nothing of another instance's is written
+    if (auto r = bake_light_records(ctx, a.moved); r != LRHIP_OK) { return r; }
     // every node of every level, from the deepest level up (restricting the refit to the ancestors of moved triangles: not done)
     for (auto l = ctx->level_offsets.size() - 1u; l-- > 0u;) {
         const auto first = ctx->level_offsets[l], n = ctx->level_offsets[l + 1u] - first;
@@ -167,7 +186,7 @@ uint64_t lrhip_scene_table_bytes(lrhip_ctx *ctx, uint32_t which) {
 
 int lrhip_read_scene_table(lrhip_ctx *ctx, uint32_t which, uint64_t byte_offset, uint64_t bytes, void *out) {
     if (ctx == nullptr || !ctx->scene_ready) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: no scene uploaded"); }
-    if (which > LRHIP_TABLE_SHADE_TRIANGLES && which != LRHIP_TABLE_VERTICES) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: unknown table"); }
+    if (which > LRHIP_TABLE_SHADE_TRIANGLES && which != LRHIP_TABLE_VERTICES && which != LRHIP_TABLE_LIGHT_INSTANCES && which != LRHIP_TABLE_LIGHT_TRIANGLES) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: unknown table"); }
     const void *base = nullptr;
     const auto size = table_bytes(ctx, which, &base);
     if (byte_offset > size || bytes > size - byte_offset) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: the range is not inside the table"); }

@@ -1,7 +1,7 @@
 // lrhip_internal.h — what the host sources of liblrhip.so share behind include/lrhip.h: the context, device buffers, error reporting, the
 // nominal-grid constants, the kernel table and the selection rule's declarations.  The sources, by responsibility:
 //   lrhip_context.hip    context, setters, film binding / download, counters; the small film kernels (film_kernels.h) and their launchers
-//   lrhip_tables.hip     host-side checks and tables of an upload: index validation, 8-bit texel packing, the time-dependent tables
+//   lrhip_tables.hip     host-side checks and tables of an upload: index validation, 8-bit texel packing, the time-dependent tables; the light sample's records
 //   lrhip_upload.hip     lrhip_upload_scene (in named steps) / lrhip_update_scene
 //   lrhip_kernels.hip    the table of compiled kernels (variants.h), the selection rule (plan_kernels), occupancy
 //   lrhip_render.hip     work items, fixed-point film, lrhip_render (one path per lane, pool, AOV)
@@ -36,6 +36,7 @@
 
 #include "megapath_kernel.h"
 #include "megapool_kernel.h"
+#include "light_record_kernels.h"
 #include "query_columns.h"
 #include "variants.h"
 
@@ -220,6 +221,10 @@ struct lrhip_ctx {
     // handle[0] of every instance record as lrhip_upload_scene / lrhip_update_scene wrote it (the mesh index and the shape's property flags;
     // no device update changes it): the rasteriser needs no read-back
     std::vector<uint32_t> instance_handles;
+    // the light sample's records (dev_scene.h: DLightInstance, DLightTri; lrhip_tables.hip: bake_light_records).  Of the uploaded scene (in
+    // scene_buffers): the light instance that owns each triangle record, and the two tables' sizes
+    const uint32_t *light_tri_owner{nullptr};
+    uint32_t light_record_count{0u}, light_tri_count{0u};
     lrh::Timer lightmap_timer, gather_timer;// (gather_timer: the gather vertex query's, lrhip_gather.hip)
 };
 
@@ -284,6 +289,14 @@ std::vector<uint8_t> build_padded_triangles(const lr_scene *s);
 std::vector<lrd::DInstance> build_instances(const lr_scene *s);
 std::vector<lrd::DShadeTri> build_shade_tris(const lr_scene *s, const std::vector<lrd::DInstance> &instances, std::string &error);
 void set_camera(lrd::DScene &d, const lr_scene *s);
+// The light sample's records.  upload_light_records: allocates the two tables of the scene being uploaded (their buffers join scene_buffers),
+// writes what the host knows -- per light instance its ids and bases, per triangle record its owner -- and bakes every record.
+// bake_light_records: the kernels of light_record_kernels.h on the context's stream, over the light instances whose instance has its bit set
+// in `moved` (a bit per instance in device memory), or over all of them (nullptr); nothing is launched for a scene without lights
+int upload_light_records(lrhip_ctx *ctx, const lr_scene *s);
+int bake_light_records(lrhip_ctx *ctx, const uint32_t *moved);
+// (lrhip_instance_update.hip: light_triangle_record over `args` with that unit's arithmetic, for DScene::light_tris_exact)
+hipError_t launch_light_triangles_exact(lrhip_ctx *ctx, const lrd::LightRecordArgs &args);
 
 // lrhip_render.hip
 struct Chunking {
@@ -310,8 +323,8 @@ hipError_t launch_wf_carry(lrhip_ctx *ctx, uint32_t margin, uint32_t mode);
 // lrhip_instance_update.hip, for the calls that move geometry on the device (the __global__ functions of instance_update_kernels.h live in
 // that object).  The call's scratch is an owner word per instance, then a bit per instance.  clear_update_scratch: sizes it for the uploaded
 // scene and clears it on the context's stream.  update_moved_mask: its bit per instance, valid after clear_update_scratch.
-// rebake_and_refit: instance_triangle_kernel over the instances whose bit is set, then instance_refit_kernel level by level from the
-// deepest up, on the context's stream
+// rebake_and_refit: instance_triangle_kernel over the instances whose bit is set, the light sample's records of those instances
+// (bake_light_records), then instance_refit_kernel level by level from the deepest up, on the context's stream
 int clear_update_scratch(lrhip_ctx *ctx);
 uint32_t *update_moved_mask(lrhip_ctx *ctx);
 int rebake_and_refit(lrhip_ctx *ctx);

@@ -6,6 +6,7 @@
 // lrhip_bsdf.o and for its reason (Makefile: lrhip_light_FLAGS): a query hands single answers to its caller
 #define LR_CALL __device__ __noinline__
 #define LR_ENV_TREE_WALK 1
+#define LR_EXACT_ARITHMETIC_UNIT 1// (Makefile: this unit's flags; kernel_forms.h: LR_LIGHT_TRIS)
 #include "lrhip_internal.h"
 #include "light_kernel.h"
 

@@ -1,8 +1,20 @@
 // lrhip_tables.hip — what lrhip_upload_scene / lrhip_update_scene put on the device, built on the host: the check of every index a
-// scene table holds into another, the 8-bit texel packing, and the tables that depend on the scene time.
+// scene table holds into another, the 8-bit texel packing, and the tables that depend on the scene time; and the one pair of tables that is
+// built ON THE DEVICE, the light sample's records (light_record_kernels.h), whose kernels stand here because this unit is built with the
+// library's own flags.
 #include "lrhip_internal.h"
 
 #include <limits>
+
+namespace lrd {
+// one thread per record (light_record_kernels.h), with this unit's arithmetic: the library's own (DScene::light_tris)
+__global__ void __launch_bounds__(kLightRecordBlock) light_instance_record_kernel(LightRecordArgs a) {
+    light_instance_record(a, blockIdx.x * kLightRecordBlock + threadIdx.x);
+}
+__global__ void __launch_bounds__(kLightRecordBlock) light_triangle_record_kernel(LightRecordArgs a) {
+    light_triangle_record(a, blockIdx.x * kLightRecordBlock + threadIdx.x);
+}
+}// namespace lrd
 
 namespace lrh {
 
@@ -166,6 +178,78 @@ std::vector<lrd::DShadeTri> build_shade_tris(const lr_scene *s, const std::vecto
         r.inst = bt.inst, r.prim = bt.prim, r.tri_offset = mesh.triangle_offset;
     }
     return shade;
+}
+
+// ---- the light sample's records (dev_scene.h: DLightInstance, DLightTri): laid out here, filled on the device
+int upload_light_records(lrhip_ctx *ctx, const lr_scene *s) {
+    auto &d = ctx->scene;
+    std::vector<lrd::DLightInstance> records(s->light_instance_count);
+    std::vector<uint32_t> owner;
+    for (uint32_t i = 0u; i < s->light_instance_count; i++) {
+        auto &r = records[i];
+        std::memset(&r, 0, sizeof(r));
+        const auto id = s->light_instances[i].instance_id;// (validate_indices: inside the instance table, its mesh inside the mesh table)
+        const auto &handle = s->instances[id].handle;
+        const auto &mesh = s->meshes[handle.x >> 10u];
+        r.instance_id = id, r.alias_base = mesh.triangle_offset, r.alias_count = handle.z;
+        r.tri_base = static_cast<uint32_t>(owner.size());
+        // one record per slot the alias table can name: the mesh's triangles (handle.z is their number in every scene the host library builds)
+        const auto count = std::max(mesh.triangle_count, handle.z);
+        if (owner.size() + count > 0x7fffffffull / sizeof(lrd::DLightTri)) {
+            return fail(LRHIP_ERROR_UNSUPPORTED, "lrhip_upload_scene: more than 2 GiB of emissive triangle records");
+        }
+        owner.insert(owner.end(), count, i);
+    }
+    auto upload = [&](const void *host, size_t bytes, const void **device) {
+        DeviceBuffer b;
+        b.bytes = std::max<size_t>(bytes, 16u);
+        LR_HIP_CHECK(hipMalloc(&b.ptr, b.bytes));
+        ctx->scene_buffers.emplace_back(b);
+        if (host == nullptr) { LR_HIP_CHECK(hipMemset(b.ptr, 0, b.bytes)); }
+        else if (bytes != 0u) { LR_HIP_CHECK(hipMemcpy(b.ptr, host, bytes, hipMemcpyHostToDevice)); }
+        *device = b.ptr;
+        return static_cast<int>(LRHIP_OK);
+    };
+    const void *dev_records = nullptr, *dev_tris = nullptr, *dev_exact = nullptr, *dev_owner = nullptr;
+    if (auto r = upload(records.data(), records.size() * sizeof(records[0]), &dev_records); r != LRHIP_OK) { return r; }
+    if (auto r = upload(nullptr, owner.size() * sizeof(lrd::DLightTri), &dev_tris); r != LRHIP_OK) { return r; }
+    if (auto r = upload(nullptr, owner.size() * sizeof(lrd::DLightTri), &dev_exact); r != LRHIP_OK) { return r; }
+    if (auto r = upload(owner.data(), owner.size() * sizeof(uint32_t), &dev_owner); r != LRHIP_OK) { return r; }
+    d.light_records = static_cast<const lrd::DLightInstance *>(dev_records), d.light_tris = static_cast<const lrd::DLightTri *>(dev_tris);
+    d.light_tris_exact = static_cast<const lrd::DLightTri *>(dev_exact);
+    ctx->light_tri_owner = static_cast<const uint32_t *>(dev_owner);
+    ctx->light_record_count = s->light_instance_count, ctx->light_tri_count = static_cast<uint32_t>(owner.size());
+    // (the tables the kernels read are on the device: instances, vertices, triangles, tri_pdf; update_counts is not set yet)
+    ctx->update_counts[2] = s->instance_count, ctx->update_counts[3] = static_cast<uint32_t>(s->triangle_count), ctx->vertex_count = s->vertex_count;
+    if (auto r = bake_light_records(ctx, nullptr); r != LRHIP_OK) { return r; }
+    LR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return LRHIP_OK;
+}
+
+int bake_light_records(lrhip_ctx *ctx, const uint32_t *moved) {
+    if (ctx->light_record_count == 0u) { return LRHIP_OK; }
+    const auto &d = ctx->scene;
+    lrd::LightRecordArgs a{};
+    a.records = const_cast<lrd::DLightInstance *>(d.light_records), a.record_count = ctx->light_record_count;
+    a.tris = const_cast<lrd::DLightTri *>(d.light_tris), a.tri_count = ctx->light_tri_count;
+    a.tri_owner = ctx->light_tri_owner;
+    a.instances = d.instances, a.instance_count = ctx->update_counts[2];
+    a.vertices = d.vertices, a.vertex_count = static_cast<uint32_t>(std::min<uint64_t>(ctx->vertex_count, 0xffffffffull));
+    a.triangles = d.triangles, a.mesh_triangle_count = ctx->update_counts[3];
+    a.tri_pdf = d.tri_pdf;
+    a.moved = moved;
+    const dim3 block(lrd::kLightRecordBlock);
+    const auto blocks_for = [](uint32_t n) { return dim3((n + lrd::kLightRecordBlock - 1u) / lrd::kLightRecordBlock); };
+    hipLaunchKernelGGL(lrd::light_instance_record_kernel, blocks_for(a.record_count), block, 0, ctx->stream, a);
+    LR_HIP_CHECK(hipGetLastError());
+    if (a.tri_count != 0u) {
+        hipLaunchKernelGGL(lrd::light_triangle_record_kernel, blocks_for(a.tri_count), block, 0, ctx->stream, a);
+        LR_HIP_CHECK(hipGetLastError());
+        // the same records once more for the kernels built without contraction, by a unit that is built as they are
+        a.tris = const_cast<lrd::DLightTri *>(d.light_tris_exact);
+        LR_HIP_CHECK(launch_light_triangles_exact(ctx, a));
+    }
+    return LRHIP_OK;
 }
 
 void set_camera(lrd::DScene &d, const lr_scene *s) {

@@ -438,6 +438,7 @@ int upload_scene_tables(lrhip_ctx *ctx, const lr_scene *s) {
         if (!error.empty()) { return fail(LRHIP_ERROR_INVALID, "lrhip_upload_scene: " + error); }
         LR_UP(upload(ctx, shade.data(), shade.size(), &d.shade_tris));
     }
+    LR_UP(upload_light_records(ctx, s));// (reads the instance, vertex, triangle and pdf tables above on the device)
     LR_UP(upload_surfaces(ctx, s));
     // the surfaces' own closure bits, before the integrator's class rewrites ctx->features below: what picks a BSDF query's kernel
     ctx->closure_features = ctx->features & (lrd::kFeatDisney | lrd::kFeatMix | lrd::kFeatLayered);
@@ -582,6 +583,8 @@ int lrhip_update_scene(lrhip_ctx *ctx, const lr_scene *s) {
     LR_HIP_CHECK(copy(ctx->nodes32, s->accel.nodes, static_cast<size_t>(s->accel.node_count) * sizeof(lr_bvh4_node)));
     // ... and the object-space vertices it, and lrhip_set_mesh_vertices, re-bake from: either side may have deformed a mesh since
     LR_HIP_CHECK(copy(d.vertices, s->vertices, static_cast<size_t>(s->vertex_count) * sizeof(lr_vertex)));
+    // the light sample's records follow the instances and vertices just copied (an animated emitter: re-baked per shutter sample)
+    if (auto r = bake_light_records(ctx, nullptr); r != LRHIP_OK) { return r; }
     LR_HIP_CHECK(hipStreamSynchronize(ctx->stream));// the host vectors above go out of scope
     set_camera(d, s);
     if (d.env_kind == lrd::kEnvConstant) {

@@ -35,6 +35,7 @@ static_assert(LR_DEFAULT_ENV_TREE == lrd::forms::walks_env_tree(LR_VARIANT), "ke
 static_assert(LR_DEFAULT_NEST == lrd::forms::nests_closures(LR_VARIANT), "kernel_forms.h: LR_NEST");
 static_assert(LR_DEFAULT_STRAIGHT_TAIL == lrd::forms::straight_tail(LR_VARIANT), "kernel_forms.h: LR_STRAIGHT_TAIL");
 static_assert(LR_DEFAULT_LEAF_TAIL_ONE_COMPARE == lrd::forms::leaf_tail_one_compare(LR_VARIANT), "kernel_forms.h: LR_LEAF_TAIL_ONE_COMPARE");
+static_assert(LR_DEFAULT_LIGHT_RECORDS == lrd::forms::light_records(LR_VARIANT), "kernel_forms.h: LR_LIGHT_RECORDS");
 
 namespace lrd {
 template __global__ void LR_KERNEL<LR_VARIANT>(DScenePtr, RenderArgs);
