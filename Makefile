@@ -216,13 +216,21 @@ $(LIBDIR)/variants/liblrhip_nostraight.so: $(HIP_SRC) $(HIPDIR)/megapath_variant
 	$(MAKE) --no-print-directory hip-variant NAME=nostraight DEFS='-DLR_STRAIGHT_TAIL=0' VARIANT_MASKS='0 1 4096 4097 4098 4099 4100 4101 4102 4103 4116 4117 20482 20483 12308 12309' HEAVY_MASKS=
 
 # Kernels once more WITHOUT the light sample's records (dev_shade.h: LR_LIGHT_RECORDS): a light sample walks light instance -> instance -> alias
-# entry -> triangle indices -> three vertices and computes the emissive triangle's normal and area per sample.  The lean one-path kernels <0> - <3> (of them <2> and <3> take the
-# records in the shipped library, kernel_forms.h) and the masks of `noride`.  TEST INFRASTRUCTURE: the records hold what that code computes, from the same function
-# (dev_shade.h: triangle_constants), so the shipped library's frames, its counters and its light queries must equal this library's
-# (tests/test_gpu_light_records.py).
+# entry -> triangle indices -> three vertices and computes the emissive triangle's normal and area per sample.  TEST INFRASTRUCTURE: the records hold
+# what that code computes, from the same function (dev_shade.h: triangle_constants), so the shipped library's frames, its counters and its queries must
+# equal this library's (tests/test_gpu_light_records.py).  It holds one record-reading kernel of every family, with its counting twin where the test
+# compares counters: the lean one-path kernels <0> - <3> (of them <2> and <3> take the records in the shipped library, kernel_forms.h) and the masks of
+# `noride` (of them <20482> is the PaddedSobol pool kernel the test runs); lean + alpha <8>, lean + Disney <16>, environment + Disney <20>; <60>, <124>,
+# nested <636>; the sibling integrators <252>; AOV <32892>; the volumetric kernel <256>; the camera and continuation passes of wavefront mode
+# <1024> <3072> with the heavy kernels of the three closure kinds, and the pool's <5120> <7168>; the gather kernel <196734>; the radiance query
+# kernel <65660>.  The define goes to the units built with VPT_HIPFLAGS too (the volumetric and gather kernels: variant_flags), which HIPFLAGS does not reach.
+NOLIGHTREC_MASKS := 0 1 2 3 4096 4097 4098 4099 4100 4101 4102 4103 4116 4117 20482 20483 12308 12309 \
+    8 9 16 17 20 21 60 61 124 125 636 252 32892 256 1024 1025 3072 3073 5120 7168 196734 65660
+NOLIGHTREC_HEAVY := 0 1 4 5 8 9
 nolightrec: $(LIBDIR)/variants/liblrhip_nolightrec.so
-$(LIBDIR)/variants/liblrhip_nolightrec.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIP_HDR) Makefile
-	$(MAKE) --no-print-directory hip-variant NAME=nolightrec DEFS='-DLR_LIGHT_RECORDS=0' VARIANT_MASKS='0 1 2 3 4096 4097 4098 4099 4100 4101 4102 4103 4116 4117 20482 20483 12308 12309' HEAVY_MASKS=
+$(LIBDIR)/variants/liblrhip_nolightrec.so: $(HIP_SRC) $(HIPDIR)/megapath_variant.hip $(HIPDIR)/heavy_variant.hip $(HIP_HDR) Makefile
+	$(MAKE) --no-print-directory hip-variant NAME=nolightrec DEFS='-DLR_LIGHT_RECORDS=0' VPT_HIPFLAGS='$(VPT_HIPFLAGS) -DLR_LIGHT_RECORDS=0' \
+	    VARIANT_MASKS='$(NOLIGHTREC_MASKS)' HEAVY_MASKS='$(NOLIGHTREC_HEAVY)'
 
 cli: $(BINDIR)/luisa-render-cli
 $(BINDIR)/luisa-render-cli: $(HOSTDIR)/cli.cpp $(HOSTDIR)/plugin_megapath.cpp $(LIBDIR)/liblrhost.so $(HOST_HDR)

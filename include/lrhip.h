@@ -911,6 +911,7 @@ int lrhip_plan_kernels(uint32_t features, uint32_t force_features, uint32_t flag
  * on the device: 96 bytes per light instance (its instance id, the base and length of its alias table, its first triangle record; the shape's
  * property flags, tags and offset bits; the four columns of object_to_world, a quad each) and 80 bytes per (light instance, primitive)
  * (object-space p0 p1 p2 with the world-space geometric normal in the quads' fourth words; uv0 uv1; uv2, world-space area, pdf table entry).
+ * Table 18 is table 17 once more, as the units without fp contraction bake it (the volumetric and gather kernels, the light and gather queries).
  * LRHIP_ERROR_INVALID before any upload, for an unknown table and for a range that is not inside the table.                              */
 #define LRHIP_TABLE_NODES 0u
 #define LRHIP_TABLE_BVH_TRIANGLES 1u
@@ -919,6 +920,7 @@ int lrhip_plan_kernels(uint32_t features, uint32_t force_features, uint32_t flag
 #define LRHIP_TABLE_VERTICES 8u
 #define LRHIP_TABLE_LIGHT_INSTANCES 16u
 #define LRHIP_TABLE_LIGHT_TRIANGLES 17u
+#define LRHIP_TABLE_LIGHT_TRIANGLES_EXACT 18u
 int lrhip_read_scene_table(lrhip_ctx *ctx, uint32_t which, uint64_t byte_offset, uint64_t bytes, void *out);
 /* size in bytes of that table in the uploaded scene (0: none, or an unknown table) */
 uint64_t lrhip_scene_table_bytes(lrhip_ctx *ctx, uint32_t which);

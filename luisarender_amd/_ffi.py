@@ -242,9 +242,9 @@ class MeshUpdateParams(C.Structure):
 
 # lrhip_read_scene_table's tables (LRHIP_TABLE_*) and the bytes of one record of each (ids 4 to 7 name no table)
 TABLE_NODES, TABLE_BVH_TRIANGLES, TABLE_INSTANCES, TABLE_SHADE_TRIANGLES, TABLE_VERTICES = 0, 1, 2, 3, 8
-TABLE_LIGHT_INSTANCES, TABLE_LIGHT_TRIANGLES = 16, 17  # the light sample's records, built on the device
+TABLE_LIGHT_INSTANCES, TABLE_LIGHT_TRIANGLES, TABLE_LIGHT_TRIANGLES_EXACT = 16, 17, 18  # the light sample's records, built on the device
 TABLE_RECORD_BYTES = {TABLE_NODES: 64, TABLE_BVH_TRIANGLES: 48, TABLE_INSTANCES: 128, TABLE_SHADE_TRIANGLES: 128, TABLE_VERTICES: 32,
-                      TABLE_LIGHT_INSTANCES: 96, TABLE_LIGHT_TRIANGLES: 80}
+                      TABLE_LIGHT_INSTANCES: 96, TABLE_LIGHT_TRIANGLES: 80, TABLE_LIGHT_TRIANGLES_EXACT: 80}
 
 RAY_CLOSEST, RAY_ANY = 0, 1  # LRHIP_RAY_CLOSEST / LRHIP_RAY_ANY
 RAY_DEVICE_POINTERS, RAY_ALPHA_TEST = 1, 2  # LRHIP_RAY_DEVICE_POINTERS / LRHIP_RAY_ALPHA_TEST

@@ -44,6 +44,7 @@ size_t table_bytes(const lrhip_ctx *ctx, uint32_t which, const void **base) {
         case LRHIP_TABLE_VERTICES: *base = d.vertices; return static_cast<size_t>(ctx->vertex_count) * sizeof(lr_vertex);
         case LRHIP_TABLE_LIGHT_INSTANCES: *base = d.light_records; return static_cast<size_t>(ctx->light_record_count) * sizeof(lrd::DLightInstance);
         case LRHIP_TABLE_LIGHT_TRIANGLES: *base = d.light_tris; return static_cast<size_t>(ctx->light_tri_count) * sizeof(lrd::DLightTri);
+        case LRHIP_TABLE_LIGHT_TRIANGLES_EXACT: *base = d.light_tris_exact; return static_cast<size_t>(ctx->light_tri_count) * sizeof(lrd::DLightTri);
         default: return 0u;
     }
 }
@@ -186,7 +187,8 @@ uint64_t lrhip_scene_table_bytes(lrhip_ctx *ctx, uint32_t which) {
 
 int lrhip_read_scene_table(lrhip_ctx *ctx, uint32_t which, uint64_t byte_offset, uint64_t bytes, void *out) {
     if (ctx == nullptr || !ctx->scene_ready) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: no scene uploaded"); }
-    if (which > LRHIP_TABLE_SHADE_TRIANGLES && which != LRHIP_TABLE_VERTICES && which != LRHIP_TABLE_LIGHT_INSTANCES && which != LRHIP_TABLE_LIGHT_TRIANGLES) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: unknown table"); }
+    if (which > LRHIP_TABLE_SHADE_TRIANGLES && which != LRHIP_TABLE_VERTICES && which != LRHIP_TABLE_LIGHT_INSTANCES && which != LRHIP_TABLE_LIGHT_TRIANGLES &&
+        which != LRHIP_TABLE_LIGHT_TRIANGLES_EXACT) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: unknown table"); }
     const void *base = nullptr;
     const auto size = table_bytes(ctx, which, &base);
     if (byte_offset > size || bytes > size - byte_offset) { return fail(LRHIP_ERROR_INVALID, "lrhip_read_scene_table: the range is not inside the table"); }

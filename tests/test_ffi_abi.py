@@ -38,6 +38,18 @@ def test_hip_library_exports_header_symbols():
         assert hasattr(lib, n), n
 
 
+def test_scene_table_ids_match_the_header():
+    """lrhip_read_scene_table's table ids (LRHIP_TABLE_*): every one of the header has its _ffi.TABLE_* twin with the same number and a record size"""
+    text = open(os.path.join(_ffi.REPO_ROOT, "include", "lrhip.h")).read()
+    ids = {name: int(value) for name, value in re.findall(r"^#define LRHIP_TABLE_([A-Z_]+) (\d+)u$", text, flags=re.M)}
+    assert len(ids) == 8 and len(set(ids.values())) == 8
+    for name, value in ids.items():
+        assert getattr(_ffi, "TABLE_" + name) == value and value in _ffi.TABLE_RECORD_BYTES, name
+    assert sorted(_ffi.TABLE_RECORD_BYTES) == sorted(ids.values())
+    assert ids["LIGHT_TRIANGLES_EXACT"] == ids["LIGHT_TRIANGLES"] + 1 == 18  # the next free number
+    assert _ffi.TABLE_RECORD_BYTES[_ffi.TABLE_LIGHT_TRIANGLES_EXACT] == _ffi.TABLE_RECORD_BYTES[_ffi.TABLE_LIGHT_TRIANGLES] == 80
+
+
 def test_oracle_exports():
     lib = oracle_lib()
     for n in _declared("../oracle/oracle.h", "oracle"):

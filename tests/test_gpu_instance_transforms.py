@@ -262,6 +262,8 @@ def test_errors(pair):
     size = int(lib.lrhip_scene_table_bytes(ra._ctx, _ffi.TABLE_INSTANCES))
     assert size == 5 * 128 and lib.lrhip_read_scene_table(ra._ctx, _ffi.TABLE_INSTANCES, size - 64, 128, (C.c_uint8 * 128)()) == LRHIP_ERROR_INVALID
     assert lib.lrhip_read_scene_table(ra._ctx, 4, 0, 0, None) == LRHIP_ERROR_INVALID
+    unknown = max(_ffi.TABLE_RECORD_BYTES) + 1  # the first number behind the last table (18: the exact-arithmetic light triangles)
+    assert unknown == 19 and lib.lrhip_read_scene_table(ra._ctx, unknown, 0, 0, None) == LRHIP_ERROR_INVALID and lib.lrhip_scene_table_bytes(ra._ctx, unknown) == 0
     assert_equal_tables(tables(ra), start, "refused calls change nothing")
     # a device-pointer list with one id out of range: that entry is left out, the others are applied
     skipped = torch.from_numpy(np.stack([matrices[0], S.srt(translate=(9, 9, 9)), matrices[1], matrices[2]])).to("cuda:0")

@@ -18,7 +18,12 @@ The scenes, at 16 x 16 or 24 x 24 pixels, 2 to 8 spp, depth <= 4: the Cornell bo
 vertex uvs and a checkerboard (per-sample, `dynamic`) emission; a quad under a non-uniform scale and a rotation, one-sided and two-sided; two
 instances of one emissive mesh; emitters under a constant environment with 0 < env_prob < 1; no light at all (empty tables, nothing read).
 lrhip_set_mesh_vertices refuses a mesh with an emissive instance (its alias table is not rebuilt on the device), so no record can go stale
-through it: the test holds that refusal and that the records stay."""
+through it: the test holds that refusal and that the records stay.
+
+Further down, one record-reading kernel of every other family against the same twin (FAMILIES, the two query families), each asserted NOT to be
+one of the kernels that keep the chain in the shipped library (csrc/hip/kernel_forms.h: LR_MASK_KEEPS_LIGHT_GATHERS, read off the header), on a scene
+whose three emitters have 320, 2 and 80 triangles; and a four-triangle emitter with a triangle without area, end to end.  The tables' CONTENT is
+judged against float64 in tests/test_gpu_light_record_tables.py."""
 import os
 
 import numpy as np
@@ -290,3 +295,270 @@ def test_an_emissive_mesh_is_not_deformed_and_its_records_stay():
         assert np.array_equal(r.scene_table(_ffi.TABLE_LIGHT_TRIANGLES), before[1])
     finally:
         r.close()
+
+
+# ---- every family of kernels that reads the records, against the chain of gathers ----------------------------------------------------------------
+# The cases above reach <4096>, <2> and the light query unit.  `make nolightrec` also holds one record-reading kernel of every other family
+# (Makefile: NOLIGHTREC_MASKS); each case below renders or queries one scene on the shipped library and on the twin and holds the answers to
+# each other bit for bit.  The scenes' emitters tell records apart: three light instances of 320, 2 and 80 triangles -- a wrong tri_base, alias_base
+# or table shows -- the first of them an icosphere with vertex uvs under a checkerboard emission.
+ENV, ALPHA, DISNEY, MIX, LAYERED, AUX, VPT, NEST, WF, CONT, PADDED, AOV, QUERY, GATHER = 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 16384, 32768, 65536, 131072
+_CUTOUT = "Surface NAME : Matte { Kd : Constant { v { 0.7, 0.6, 0.2 } } alpha : Checkerboard { on : Constant { v { 1 } } off : Constant { v { 0.2 } } scale { 3 } } }"
+_MATTE = "Surface NAME : Matte { Kd : Constant { v { 0.7, 0.3, 0.2 } } }"
+
+
+def _keep_list() -> set:
+    """the masks of LR_MASK_KEEPS_LIGHT_GATHERS, read off csrc/hip/kernel_forms.h (each stands for itself and its counting twin)"""
+    import re
+    text = open(os.path.join(_ffi.REPO_ROOT, "luisarender_amd", "csrc", "hip", "kernel_forms.h")).read()
+    body = re.search(r"#define LR_MASK_KEEPS_LIGHT_GATHERS\(M\)((?:.*\\\n)*.*\n)", text).group(1)
+    masks = {int(m) for m in re.findall(r"LR_MASK_OR_TWIN\(M, (\d+)\)", body)}
+    assert len(masks) == 25 and 0 in masks and 4116 in masks, masks
+    return masks
+
+
+def _reads_records(mask: int) -> bool:
+    return (mask & ~1) not in _keep_list()
+
+
+def _surface(name: str, material: str) -> str:
+    from helpers import MATERIALS
+    text = {"matte": _MATTE, "cutout": _CUTOUT}.get(material) or MATERIALS[material].replace("Surface m ", "Surface NAME ")
+    return text.replace("NAME", name) + "\n"
+
+
+_SUN = "environment : Directional { emission : Constant { v { 3, 2.5, 2 } } angle { 40 } direction { 0.1, -1, 0.2 } }"  # (a constant one needs no kernel of the environment bit)
+
+
+def _family_scene(surfaces=("matte", "matte", "matte"), environment="", integrator="MegaPath {", sampler="Independent", extra="") -> str:
+    """a room (open to the environment, if there is one) with two balls and a card under three emitters"""
+    v, f, n = icosphere(2)
+    assert len(f) == 320
+    uv = np.stack([np.arctan2(v[:, 2], v[:, 0]) / (2 * np.pi) + 0.5, np.arccos(np.clip(v[:, 1], -1, 1)) / np.pi], -1)
+    glow = inline_mesh("glow", v * 0.5, f, n, uv)
+    assert glow.endswith("}\n")
+    glow = glow[:-2] + ("  light : Diffuse { emission : Checkerboard { on : Constant { v { 9, 6, 2 } } off : Constant { v { 1, 3, 8 } } scale { 6 } } }\n"
+                        "  transform : SRT { scale { 1, 0.7, 1.2 } rotate { 0, 1, 1, 30 } translate { 0.5, 3.4, 0.3 } }\n}\n")
+    room = _HEAD.split("Shape ball")[0]
+    if environment:
+        room = room.replace("4,5,6, 4,6,7, ", "")
+    text = "".join(_surface(f"s{k}", m) for k, m in enumerate(surfaces)) + extra + room + glow + f"""
+Shape ball : Sphere {{ subdivision {{ 1 }} surface {{ @s0 }} transform : SRT {{ scale {{ 0.8, 0.8, 0.8 }} translate {{ -1.25, 0.8, 0 }} }} }}
+Shape ball2 : Sphere {{ subdivision {{ 1 }} surface {{ @s1 }} transform : SRT {{ scale {{ 0.6, 0.6, 0.6 }} translate {{ 1.3, 0.6, 0.6 }} }} }}
+Shape card : {_QUAD} surface {{ @s2 }} transform : SRT {{ scale {{ 2, 1, 2 }} rotate {{ 1, 0, 0, 20 }} translate {{ 0, 0.4, 1.2 }} }} }}
+Shape lamp : {_QUAD} light : Diffuse {{ emission : Constant {{ v {{ 12, 11, 9 }} }} two_sided {{ true }} }}
+  transform : SRT {{ scale {{ 1.5, 1, 0.4 }} rotate {{ 1, 0.3, 0.2, 25 }} translate {{ -1.2, 3.6, -0.8 }} }} }}
+Shape bulb : Sphere {{ subdivision {{ 1 }} light : Diffuse {{ emission : Constant {{ v {{ 2, 8, 3 }} }} two_sided {{ true }} }}
+  transform : SRT {{ scale {{ 0.25, 0.4, 0.25 }} translate {{ 1.8, 2.6, -1.2 }} }} }}
+Camera cam : Pinhole {{ spp {{ 2 }} film : Color {{ resolution {{ 24, 24 }} }} position {{ 0, 2.5, 8.5 }} look_at {{ 0, 2, 0 }} fov {{ 40 }} }}
+render {{ cameras {{ @cam }} shapes {{ @room, @glow, @ball, @ball2, @card, @lamp, @bulb }} {environment}
+  integrator : {integrator} depth {{ 3 }} sampler : {sampler} {{ seed {{ 11 }} }} }} }}
+"""
+    return text
+
+
+# family: (scene arguments, what runs: pool scheduler / wavefront mode, the kernel it lands on, whether the twin holds its counting twin,
+# whether the case is run once more after a device move of an emitter)
+FAMILIES = {
+    "alpha": (dict(surfaces=("cutout", "matte", "matte")), dict(pool=False), ALPHA, True, False),
+    "disney": (dict(surfaces=("disney", "matte", "disney_thin")), dict(pool=False), DISNEY, True, False),
+    "env_disney": (dict(surfaces=("disney", "matte", "matte"), environment=_SUN), dict(pool=False), ENV | DISNEY, True, False),
+    "mix": (dict(surfaces=("mix", "cutout", "disney"), environment=_ENV), dict(pool=False, wavefront=False), 60, True, False),
+    "layered": (dict(surfaces=("layered", "mix", "disney")), dict(pool=False, wavefront=False), 124, True, True),
+    "nested": (dict(surfaces=("mix_layered", "layered_mix", "matte")), dict(pool=False, wavefront=False), 636, False, False),
+    "direct": (dict(surfaces=("glass", "matte", "matte"), integrator='Direct { importance_sampling { "both" }'), dict(pool=False), 252, False, False),
+    "aov": (dict(surfaces=("disney", "matte", "matte"), integrator='AOV { components { "sample", "diffuse", "specular" }'), dict(pool=False), 32892, False, False),
+    "volumetric": (dict(surfaces=("glass", "matte", "matte"), integrator="MegaVPTNaive {"), dict(pool=False), VPT, False, True),
+    "wavefront": (dict(surfaces=("mix", "layered", "disney")), dict(pool=False, wavefront=True), WF, True, True),
+    "pool_wavefront": (dict(surfaces=("mix", "layered", "disney")), dict(pool=True, wavefront=True), POOL | WF, False, False),
+    "padded_pool": (dict(sampler="PaddedSobol"), dict(pool=True), PADDED | POOL | GENERIC, True, False),
+}
+
+
+def _emitter(scene) -> int:
+    """the instance of the textured icosphere: the emitter with 320 triangles"""
+    v = scene.view()
+    ids = [i for i in range(v.instance_count) if v.instances[i].handle.x & 8 and v.meshes[v.instances[i].handle.x >> 10].triangle_count == 320]
+    assert len(ids) == 1
+    return ids[0]
+
+
+def _plan(features, pool, sampler_kind, wf_mode, depth):
+    """lrhip_plan_kernels: (family, camera or main mask, continuation mask, heavy masks of Disney / Mix / Layered)"""
+    import ctypes as C
+    lib = C.CDLL(os.path.join(_ffi.LIB_DIR, "liblrhip.so"))
+    lib.lrhip_plan_kernels.argtypes = [C.c_uint32] * 6 + [C.POINTER(C.c_uint32 * 8)]
+    out = (C.c_uint32 * 8)()
+    assert lib.lrhip_plan_kernels(features, 0, (8 if pool else 0) | 16, sampler_kind, wf_mode, depth, C.byref(out)) == 0
+    return list(out)[:6]
+
+
+@pytest.mark.parametrize("family", list(FAMILIES))
+def test_every_reader_family_renders_the_frames_of_the_chain_of_gathers(family):
+    lib = _twin()
+    scene_args, run, mask, counting, moves = FAMILIES[family]
+    scene = Scene.from_string(_family_scene(**scene_args))
+    view = scene.view()
+    assert int(view.light_instance_count) == 3
+    spp = 2
+    matrix = _srt((0.8, 1.0, 1.4), (0.2, 1, 0.4), 200.0, (-0.3, 3.0, 0.6))[None]
+    target = np.array([_emitter(scene)])
+    answers = []
+    for path in (None, lib):
+        r = _renderer(path, run["pool"])
+        try:
+            if "wavefront" in run:
+                r.set_wavefront(run["wavefront"])
+            r.upload(scene)
+            rounds = []
+            for moved in ((False, True) if moves else (False,)):
+                if moved:  # the shipped library re-bakes the emitter's records; the twin reads `instances` itself: a stale record is a film difference
+                    r.set_instance_transforms(matrix, target)
+                r.clear()
+                r.render(0, spp, sync=True)
+                if family == "aov":  # (its film is the `sample` buffer)
+                    got = {c: r.download_aov(c, normalized=False) for c in ("sample", "diffuse", "specular")}
+                    got["film"], got["variant"] = got["sample"], r.last_variant()
+                else:
+                    got = {"film": r.download(False), "variant": r.last_variant()}
+                if counting:
+                    r.clear()
+                    start = r.counters()
+                    r.render(0, spp, counters=True, sync=True)
+                    got["counting film"], got["counting variant"] = r.download(False), r.last_variant()
+                    got["counters"] = {k: v - start[k] for k, v in r.counters().items() if not isinstance(v, list)}
+                rounds.append(got)
+            answers.append(rounds)
+        finally:
+            r.close()
+    for k, (a, b) in enumerate(zip(*answers)):
+        what = f"{family}{', after a device move of the emitter' if k else ''}"
+        variant = a["variant"]
+        if run.get("wavefront"):
+            closures = variant & (DISNEY | MIX | LAYERED | NEST)
+            camera = variant & ~closures
+            plan = _plan(closures, run["pool"], int(view.sampler.kind), 0, 3)
+            assert plan[0] == 3 and plan[1] == camera == mask and plan[2] == (camera | CONT) and closures == (DISNEY | MIX | LAYERED), (what, variant, plan)
+            kernels = [camera, camera | CONT]  # (the heavy kernels have no form that keeps the chain in the shipped library: kernel_forms.h)
+            print(f"{what}: camera pass <{camera}>, continuation pass <{camera | CONT}>, heavy kernels {plan[3:6]}")
+        else:
+            assert variant == mask, (what, variant, mask)
+            kernels = [variant]
+            print(f"{what}: <{variant}>")
+        for m in kernels:
+            assert _reads_records(m), (what, m, "keeps the chain of gathers in the shipped library: the case would compare the chain with itself")
+        assert b["variant"] == variant, (what, variant, b["variant"])
+        film = a["film"]
+        if family != "aov":
+            assert np.isfinite(film).all() and (film[..., 3] == spp).all() and film[..., :3].sum() > 0, what
+        assert np.array_equal(film.view(np.uint32), b["film"].view(np.uint32)), f"{what}: the films differ"
+        if family == "aov":
+            for c in ("sample", "diffuse", "specular"):
+                assert np.array_equal(a[c].view(np.uint32), b[c].view(np.uint32)), f"{what}: the {c} buffers differ"
+            assert np.isfinite(a["sample"]).all() and a["sample"].sum() > 0
+        if counting:
+            assert a["counting variant"] == b["counting variant"] and a["counting variant"] & 1, what
+            assert np.array_equal(a["counting film"].view(np.uint32), b["counting film"].view(np.uint32)), f"{what}: counting twins: the films differ"
+            for c in EQUAL_COUNTERS:
+                assert a["counters"][c] == b["counters"][c], (what, c, a["counters"][c], b["counters"][c])
+            assert a["counters"]["nee_samples"] > 0 and a["counters"]["shadow_rays"] > 0
+    if moves:
+        assert not np.array_equal(answers[0][0]["film"], answers[0][1]["film"])
+
+
+@pytest.mark.parametrize("family", ["gather", "radiance"])
+def test_query_families_answer_as_the_chain_of_gathers(family):
+    """lrhip_gather_irradiance on <196734> (the exact-arithmetic table) and lrhip_trace_radiance on <65660>: raw sums over 1000 records, explicit streams;
+    the gather once more after a device move of the emitter.  Neither call reports its kernel: the mask is the rule of lrhip_gather.hip /
+    lrhip_radiance.hip -- the all-closures mask, | 2 for a sampler other than Independent -- and the twin holds no other kernel of either kind, where
+    a missing kernel is an error."""
+    lib = _twin()
+    sampler = "PaddedSobol" if family == "gather" else "Independent"  # (<196732>, the gather kernel of the Independent sampler, keeps the chain)
+    scene = Scene.from_string(_family_scene(surfaces=("disney", "mix", "matte"), sampler=sampler))
+    generic = GENERIC if int(scene.view().sampler.kind) != 0 else 0
+    mask = (GATHER | QUERY | 124 | generic) if family == "gather" else (QUERY | 124 | generic)
+    assert mask == (196734 if family == "gather" else 65660) and _reads_records(mask)
+    print(f"{family}: <{mask}>")
+    rng = np.random.default_rng(5)
+    n = 1000  # (no multiple of the block)
+    streams = rng.permutation(4096)[:n].astype(np.uint32)
+    points = (rng.random((n, 3)) * [5.0, 2.5, 5.0] + [-2.5, 0.2, -2.5]).astype(np.float32)
+    normals = rng.normal(size=(n, 3))
+    normals[:, 1] = np.abs(normals[:, 1])
+    normals = (normals / np.linalg.norm(normals, axis=1, keepdims=True)).astype(np.float32)
+    rays = np.zeros((n, 8), np.float32)
+    rays[:, 0:3], rays[:, 3], rays[:, 7] = points, 1e-3, 1e30
+    rays[:, 4:7] = normals
+    matrix = _srt((0.8, 1.0, 1.4), (0.2, 1, 0.4), 200.0, (-0.3, 3.0, 0.6))[None]
+    target = np.array([_emitter(scene)])
+    answers = []
+    for path in (None, lib):
+        r = _renderer(path, None)
+        try:
+            r.upload(scene)
+            ask = (lambda: r.irradiance(points=points, normals=normals, spp=4, streams=streams, raw=True)) if family == "gather" else \
+                  (lambda: r.radiance(rays, spp=4, streams=streams, raw=True))
+            got = [np.array(ask())]
+            if family == "gather":
+                r.set_instance_transforms(matrix, target)
+                got.append(np.array(ask()))
+            answers.append(got)
+        finally:
+            r.close()
+    for k, (a, b) in enumerate(zip(*answers)):
+        assert a.shape == (n, 4) and np.isfinite(a).all() and (a[:, 3] == 4).all() and a[:, :3].sum() > 0, (family, k)
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), f"{family}{', after a device move of the emitter' if k else ''}: the sums differ"
+    if family == "gather":
+        assert not np.array_equal(answers[0][0], answers[0][1])
+
+
+# ---- a triangle without area inside an emitter, end to end ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("pool", [True, False], ids=["pool", "one_path"])
+def test_a_triangle_without_area_is_never_sampled(pool):
+    """tests/light_record_scenes.py: the four-triangle emitter whose primitive 2 has two equal corners.  Its record holds area 0 and a normal that is
+    not a number (tests/test_gpu_light_record_tables.py prints it); the host gives it the probability 0 and no alias entry names it, so no sample may
+    go through it: the film is finite with every sample counted, shipped equals twin bit for bit, and no light sample carries a non-finite number."""
+    import light_record_reference as L
+    import light_record_scenes as S
+    lib = _twin()
+    spp = 4
+    scene = Scene.from_string(S.fan_text(spp=spp, resolution=24, sampler="Independent" if pool else "PaddedSobol"))
+    t = L.host_tables(scene)
+    (fan,) = [i for i in range(len(t["instances"])) if t["instances"][i, 0] & 8]
+    _, _, tri_offset, tri_count = (int(x) for x in t["meshes"][t["instances"][fan, 0] >> 10])
+    assert tri_count == S.FAN_TRIANGLES and L.expected(t)["degenerate"].tolist() == [k == S.FAN_FLAT for k in range(tri_count)]
+    import ctypes as C
+    alias = np.frombuffer(C.string_at(scene.view().tri_alias, (tri_offset + tri_count) * 8), np.uint32).reshape(-1, 2)[tri_offset:]
+    assert alias[S.FAN_FLAT, 0:1].view(np.float32)[0] == 0.0 and t["tri_pdf"][tri_offset + S.FAN_FLAT] == 0  # never kept when its slot is drawn ...
+    assert all(int(alias[k, 1]) != S.FAN_FLAT for k in range(tri_count) if alias[k, 0:1].view(np.float32)[0] < 1.0)  # ... and nobody's alias
+    rng = np.random.default_rng(3)
+    n = 4096
+    points = (rng.random((n, 3)) * [5.0, 3.0, 5.0] + [-2.5, 0.2, -2.5]).astype(np.float32)
+    u = rng.random((n, 3)).astype(np.float32)
+    results = []
+    for path in (None, lib):
+        r = _renderer(path, pool)
+        try:
+            r.upload(scene)
+            frames = _frames(r, spp)
+            results.append((frames, _light_query(r, points, u), r.scene_table(_ffi.TABLE_LIGHT_TRIANGLES)))
+        finally:
+            r.close()
+    _assert_same(results[0][0], results[1][0], spp, pool, "fan")  # finite, spp samples in every pixel, films and counters equal
+    assert results[0][0][0][..., :3].sum() > 0 and results[0][0][4]["nee_samples"] > 0
+    for a, b in zip(results[0][1], results[1][1]):
+        assert np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+    rays, radiance, pdf = results[0][1]
+    assert np.isfinite(pdf).all() and np.isfinite(radiance).all() and (pdf >= 0).all()
+    hit = pdf > 0
+    assert hit.sum() > n // 2 and np.isfinite(rays[hit]).all()
+    # the samples whose random number draws the flat triangle's slot of the alias table must come out on its alias: their points spread over an area,
+    # where the flat triangle is a segment
+    tris = results[0][2].view(np.float32)
+    assert tris[S.FAN_FLAT, 18] == 0.0 and tris[S.FAN_FLAT, 19] == 0.0 and (np.delete(tris[:, 18], S.FAN_FLAT) > 0).all()
+    slot = hit & (np.floor(u[:, 1] * tri_count) == S.FAN_FLAT)  # (dev_shade.h: alias_slot of u_light_surface.x)
+    assert slot.sum() > 100
+    p = (rays[slot, 0:3] + rays[slot, 4:7] * rays[slot, 7:8]).astype(np.float64)
+    spread = np.linalg.svd(p - p.mean(axis=0), compute_uv=False)
+    print(f"fan ({'pool' if pool else 'one path'}): {int(hit.sum())} of {n} samples with a pdf, {int(slot.sum())} drew the flat triangle's slot; singular values of their points {spread}")
+    assert spread[1] > 0.05 * spread[0]  # an area (the alias triangle), where a segment has one direction only
